@@ -1,8 +1,13 @@
 """Throughput benchmark of the L4P hot path on MI355X (contract in the task statement).
 
-  python bench.py --gpus 1 --steps K --warmup W
+  python bench.py --gpus 1 --steps K --warmup W [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step`, ...).  --full adds what takes
+passes of its own: the event-profiled second pass of the K steps (`roofline`, `roofline_<class>`, `kernel_classes`), the CPU
+baseline (`cpu_baseline`) and, for c5, the phase times of the step.  --dump-outputs DIR writes what the last timed step returned
+as DIR/<name>.npy (the inputs and weights are seeded: two builds compare output for output).
 
 A "step" = one forward of the hot path (shared encoder + the workload's heads) over one batch of
 synthetic 16x224x224 clips already resident in HBM.  One process per GPU, clips sharded with no
@@ -241,6 +246,41 @@ def cpu_baseline(sd, cfg, tasks, batch_cpu, sample_blocks: int = 0, sample_queri
                        f"+ dense heads in full {t_heads:.2f}s{track_note} -> {dt:.1f}s per clip")}
 
 
+DUMP_BUDGET_BYTES = 64 << 20   # --dump-outputs: all files together
+DUMP_ARRAY_BYTES = 4 << 20     # ... and at most this much per array (larger outputs: a fixed, seeded sample)
+
+
+def flatten_outputs(out, prefix=""):
+    """{name: tensor} of every tensor in what a step returned (nested dicts / lists / tuples; names joined with '.')."""
+    if torch.is_tensor(out):
+        return {prefix or "out": out}
+    items = out.items() if isinstance(out, dict) else enumerate(out) if isinstance(out, (list, tuple)) else ()
+    flat = {}
+    for k, v in items:
+        flat.update(flatten_outputs(v, f"{prefix}.{k}" if prefix else str(k)))
+    return flat
+
+
+def dump_outputs(out, out_dir):
+    """--dump-outputs: every tensor of ``out`` as <out_dir>/<name>.npy, float64 kept, everything else as float32.  An array
+    above its share of the 64 MB budget is replaced by a sample of its flattened values at sorted indices drawn by a generator
+    seeded from the name (the same elements in every run, so two builds compare element for element)."""
+    import zlib
+
+    import numpy as np
+
+    flat = flatten_outputs(out)
+    os.makedirs(out_dir, exist_ok=True)
+    cap = min(DUMP_ARRAY_BYTES, DUMP_BUDGET_BYTES // max(1, len(flat)) - 256)  # (256: room for the .npy header)
+    for name, t in flat.items():
+        v = t.detach().to("cpu", torch.float64 if t.dtype == torch.float64 else torch.float32)
+        keep = cap // v.element_size()
+        if v.numel() > keep:
+            g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+            v = v.reshape(-1)[torch.randint(0, v.numel(), (keep,), generator=g).sort().values]
+        np.save(os.path.join(out_dir, name + ".npy"), v.numpy())
+
+
 def build_workload(tasks, B, nq, device, rank=0, frames=16, same_data=False, use_intrinsics=None):
     """Model (name-seeded random weights, packed on rank 0 and broadcast once) + one synthetic batch of B clips."""
     cfg = ModelCfg.full()
@@ -434,40 +474,47 @@ def bench_prep(args, rank, world, device, lib):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    out = None
     for _ in range(args.steps):
-        step()
+        out = None
+        out = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
+    del out
     if world > 1:
         tt = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-    lib.l4p_prof_reset()
-    lib.l4p_prof_enable(1)
-    for _ in range(args.steps):
-        step()
-    torch.cuda.synchronize()
-    lib.l4p_prof_enable(0)
+    if not args.no_prof:
+        lib.l4p_prof_reset()
+        lib.l4p_prof_enable(1)
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        lib.l4p_prof_enable(0)
     if rank != 0:
         return
-    ms, n = read_prof(lib)["preprocess"]
-    # algorithmic bytes: every decoded frame read once (uint8) + the network input written once (float32)
-    alg = T * H * W * 3 + 3 * T_out * 224 * 224 * 4
-    ach = alg * args.steps / (ms * 1e-3) / 1e9
     res = {
         "metric": "video frames/sec prepared (resize-blur-resize, mirror-pad, 224x224 resize, normalise)",
         "value": round(world * T_out * args.steps / dt, 1), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
         "warmup": args.warmup, "ms_per_step": round(dt / args.steps * 1e3, 4), "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None, "dtype": "u8 (22-bit fixed-point filter) + f32", "data": "synthetic (seeded 480x854 uint8 video)",
         "config": {"workload": f"clip preparation: {T} decoded {H}x{W} frames -> [3,{T_out},224,224] float (one video per GPU per step)"},
-        "roofline": {"kernel": "pil_resample_{h,v}_kernel x3 + clip_resize_normalize_kernel<fused last pass>", "bound": "hbm",
-                     "achieved": round(ach, 1), "peak": 8000.0, "unit": "GB/s", "frac": round(ach / 8000.0, 4), "traffic": None,
-                     "algorithmic_bytes_per_step": alg, "kernel_ms_per_step": round(ms / args.steps, 4),
-                     "launches_per_step": n / args.steps,
-                     "method": "algorithmic bytes (frames read once + output written once) / HIP-event-bracketed kernel time"},
     }
+    if not args.no_prof:
+        ms, n = read_prof(lib)["preprocess"]
+        # algorithmic bytes: every decoded frame read once (uint8) + the network input written once (float32)
+        alg = T * H * W * 3 + 3 * T_out * 224 * 224 * 4
+        ach = alg * args.steps / (ms * 1e-3) / 1e9
+        res["roofline"] = {"kernel": "pil_resample_{h,v}_kernel x3 + clip_resize_normalize_kernel<fused last pass>", "bound": "hbm",
+                           "achieved": round(ach, 1), "peak": 8000.0, "unit": "GB/s", "frac": round(ach / 8000.0, 4), "traffic": None,
+                           "algorithmic_bytes_per_step": alg, "kernel_ms_per_step": round(ms / args.steps, 4),
+                           "launches_per_step": n / args.steps,
+                           "method": "algorithmic bytes (frames read once + output written once) / HIP-event-bracketed kernel time"}
     if world == 1 and not args.no_cpu_baseline:
         from oracle import preprocess_oracle as po
         ns = 6
@@ -510,38 +557,31 @@ def bench_demo(args, rank, world, device, lib, selftest):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    out = None
     for _ in range(args.steps):
-        step()
+        out = None
+        out = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
+    del out
     if world > 1:
         tt = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-    os.environ["L4P_TRACK_STREAMS"] = os.environ["L4P_HEAD_STREAMS"] = "0"
-    lib.l4p_prof_reset()
-    lib.l4p_prof_enable(1)
-    for _ in range(args.steps):
-        step()
-    torch.cuda.synchronize()
-    lib.l4p_prof_enable(0)
+    if not args.no_prof:
+        os.environ["L4P_TRACK_STREAMS"] = os.environ["L4P_HEAD_STREAMS"] = "0"
+        lib.l4p_prof_reset()
+        lib.l4p_prof_enable(1)
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        lib.l4p_prof_enable(0)
     if rank != 0:
         return
-    prof = read_prof(lib)
-    fl = dict(algorithmic_flops(cfg, DEMO_TASKS, nq, n_windows=nwin))  # per-window average
-    # (small / streaming dense products in their own class, FLOPs from the executed shapes: see main)
-    fl["gemm_small"] = sum(executed_flops_of_tag(tag, cfg.dim) * cnt for cls, tag, cnt, _ in read_prof_detail(lib) if cls == "gemm_small") / args.steps / nwin
-    fl["gemm"] = max(fl["gemm"] - fl["gemm_small"], 0.0)
-    classes = {}
-    for name, (ms, n) in prof.items():
-        if n:
-            ent = {"ms_per_step": round(ms / args.steps, 4), "launches_per_step": n / args.steps, "avg_launch_us": round(ms / n * 1e3, 3)}
-            if fl.get(name, 0) > 0:
-                ent["tflops"] = round(fl[name] * nwin / (ms / args.steps * 1e-3) / 1e12, 2)
-            classes[name] = ent
-    dom = max((k for k in ("gemm", "conv3d", "attention") if k in classes), key=lambda k: classes[k]["ms_per_step"])
     res = {
         "metric": "frames/sec (depth + flow + motion-seg + 2D/3D tracks), 64-frame 224x224 clip, 625 track queries",
         "value": round(world * T_out * args.steps / dt, 3), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
@@ -551,13 +591,27 @@ def bench_demo(args, rank, world, device, lib, selftest):
         "config": {"workload": f"demo generic video (demo/demo.py:84-100): 1 clip of {T_out} frames = {nwin} windows per GPU, tasks "
                                f"{'+'.join(DEMO_TASKS)}, {nq} grid queries in chunks of {net.task_heads['track_2d'].max_queries}, windows batched {net.window_batch} at a time",
                    "queries": nq, "windows": nwin, "tasks": DEMO_TASKS},
-        "roofline": {"kernel": {"gemm": "gemm8p_kernel<0> / gemm_kernel<bf16,MODE0>", "conv3d": "gemm8p_kernel<1> / gemm_kernel<bf16,MODE1>",
-                                "attention": "attn64_kernel<bf16,88> (encoder attention, one wave per SIMD, 64 query rows per wave; attn_kernel<bf16,96,64> below 256 tiles)"}[dom], "bound": "mfma", "achieved": classes[dom]["tflops"],
-                     "peak": PRECISION[ENGINE_PRECISION][2] / 1e12, "unit": "TFLOP/s", "frac": round(classes[dom]["tflops"] / (PRECISION[ENGINE_PRECISION][2] / 1e12), 4),
-                     "traffic": None, "method": "algorithmic FLOPs / HIP-event-bracketed kernel time, second pass of the same K steps",
-                     "algorithmic_flops_per_step": fl[dom] * nwin},
-        "kernel_classes": classes,
     }
+    if not args.no_prof:
+        prof = read_prof(lib)
+        fl = dict(algorithmic_flops(cfg, DEMO_TASKS, nq, n_windows=nwin))  # per-window average
+        # (small / streaming dense products in their own class, FLOPs from the executed shapes: see main)
+        fl["gemm_small"] = sum(executed_flops_of_tag(tag, cfg.dim) * cnt for cls, tag, cnt, _ in read_prof_detail(lib) if cls == "gemm_small") / args.steps / nwin
+        fl["gemm"] = max(fl["gemm"] - fl["gemm_small"], 0.0)
+        classes = {}
+        for name, (ms, n) in prof.items():
+            if n:
+                ent = {"ms_per_step": round(ms / args.steps, 4), "launches_per_step": n / args.steps, "avg_launch_us": round(ms / n * 1e3, 3)}
+                if fl.get(name, 0) > 0:
+                    ent["tflops"] = round(fl[name] * nwin / (ms / args.steps * 1e-3) / 1e12, 2)
+                classes[name] = ent
+        dom = max((k for k in ("gemm", "conv3d", "attention") if k in classes), key=lambda k: classes[k]["ms_per_step"])
+        res["roofline"] = {"kernel": {"gemm": "gemm8p_kernel<0> / gemm_kernel<bf16,MODE0>", "conv3d": "gemm8p_kernel<1> / gemm_kernel<bf16,MODE1>",
+                                      "attention": "attn64_kernel<bf16,88> (encoder attention, one wave per SIMD, 64 query rows per wave; attn_kernel<bf16,96,64> below 256 tiles)"}[dom], "bound": "mfma", "achieved": classes[dom]["tflops"],
+                           "peak": PRECISION[ENGINE_PRECISION][2] / 1e12, "unit": "TFLOP/s", "frac": round(classes[dom]["tflops"] / (PRECISION[ENGINE_PRECISION][2] / 1e12), 4),
+                           "traffic": None, "method": "algorithmic FLOPs / HIP-event-bracketed kernel time, second pass of the same K steps",
+                           "algorithmic_flops_per_step": fl[dom] * nwin}
+        res["kernel_classes"] = classes
     print(json.dumps(res))
 
 
@@ -573,16 +627,23 @@ def main():
     ap.add_argument("--use-intrinsics", action="store_true", help="camray head with given intrinsics (demo.py:215) instead of "
                                                                   "the shipped use_intrinsics=false (K estimated from the ray map)")
     ap.add_argument("--queries", type=int, default=64)
-    ap.add_argument("--group", type=int, default=16, help="c5: windows batched through encoder + dense decoders per launch group (16: whole rounds of 256x256 tiles in the encoder linears; 4 -> 16: +6.8 % on one GPU)")
+    ap.add_argument("--group", type=int, default=16, help="c5: windows batched through encoder + dense decoders per launch group (16: whole rounds of 256x256 tiles in the encoder linears; 4 -> 16: +6.8 %% on one GPU)")
     ap.add_argument("--precision", default="bf16", choices=sorted(PRECISION), help="engine dtype: bf16 (BASELINE.json's configs; default), "
                     "16-mixed (IEEE half: the reference demo's own mode), 32-true (exact-f32 parity engine)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also measure what the headline figure does not need: the event-profiled "
+                    "second pass (roofline, kernel_classes), the CPU baseline and c5's phase times.  A plain run only sets up, warms "
+                    "up, times the K steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last timed step returned as "
+                    "DIR/<name>.npy (float32 / float64, 64 MB at most: larger outputs as a fixed, seeded sample)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--cpu-baseline-quick", action="store_true",
                     help="contract tests only: time 4 encoder blocks and 8 queries and scale (the default times the whole clip)")
-    ap.add_argument("--no-prof", action="store_true")
+    ap.add_argument("--no-prof", action="store_true", help="--full without the event-profiled pass")
     ap.add_argument("--host-io", action="store_true", help="c2 / c3: after the timed steps, K more with the inputs coming from and every output going to "
                                                            "pinned host memory; reported as pcie_inclusive (never as value)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the timed steps and the line, nothing that takes a pass of its own
+        args.no_prof = args.no_cpu_baseline = True
     global ENGINE_PRECISION
     ENGINE_PRECISION = args.precision
 
@@ -626,12 +687,17 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    out = None
     for _ in range(args.steps):
-        step()
+        out = None  # (released before the next step starts, as if it were not kept)
+        out = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
+    del out
     # ---- kernel-class durations: the same K steps again with every launch bracketed by HIP events on the launch
     #      stream.  Kept out of the timed region because the event packets themselves cost ~13 % of a step at batch 1
     #      (15.1 ms -> 17.5 ms measured); kernel durations are unaffected up to a few %.
@@ -685,7 +751,7 @@ def main():
         tt = torch.tensor([dt], dtype=torch.float64, device=device)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         dt = float(tt.item())
-    phases = c5_phase_times(model.l4p_model, batch, tasks, rank, world, args.group) if c5 else None
+    phases = c5_phase_times(model.l4p_model, batch, tasks, rank, world, args.group) if c5 and args.full else None
 
     if rank != 0:
         return

@@ -17,16 +17,16 @@ rocprofv3 --pmc WRITE_SIZE --kernel-trace --output-format csv -d $O/pmc_${TAG}_w
 cd $R
 python tools/pmc_hbm_traffic.py $O/pmc_${TAG}_fetch $O/pmc_${TAG}_write $O/${TAG}_c3_hbm_traffic > /dev/null
 cp $O/${TAG}_c3_hbm_traffic.json $O/${TAG}_c3_hbm_traffic.md $R/profiles/   # (on the box; copy them into the tracked profiles/ afterwards)
-python bench.py --steps 20 --warmup 5 > $O/${TAG}_c3_bench_line.json 2> $O/${TAG}_c3.err
-python bench.py --workload c2 --steps 40 --warmup 10 > $O/${TAG}_c2_bench_line.json 2> $O/${TAG}_c2.err
-python bench.py --workload c5 --steps 3 --warmup 1 > $O/${TAG}_c5_bench_line.json 2> $O/${TAG}_c5.err
-python bench.py --workload demo --steps 3 --warmup 1 > $O/${TAG}_demo_bench_line.json 2> $O/${TAG}_demo.err
-python bench.py --workload prep --steps 50 --warmup 10 > $O/${TAG}_prep_bench_line.json 2> $O/${TAG}_prep.err
-python bench.py --batch 8 --steps 10 --warmup 3 > $O/${TAG}_c3_batch8_bench_line.json 2> $O/${TAG}_c3_batch8.err
+python bench.py --full --steps 20 --warmup 5 > $O/${TAG}_c3_bench_line.json 2> $O/${TAG}_c3.err
+python bench.py --full --workload c2 --steps 40 --warmup 10 > $O/${TAG}_c2_bench_line.json 2> $O/${TAG}_c2.err
+python bench.py --full --workload c5 --steps 3 --warmup 1 > $O/${TAG}_c5_bench_line.json 2> $O/${TAG}_c5.err
+python bench.py --full --workload demo --steps 3 --warmup 1 > $O/${TAG}_demo_bench_line.json 2> $O/${TAG}_demo.err
+python bench.py --full --workload prep --steps 50 --warmup 10 > $O/${TAG}_prep_bench_line.json 2> $O/${TAG}_prep.err
+python bench.py --full --batch 8 --steps 10 --warmup 3 > $O/${TAG}_c3_batch8_bench_line.json 2> $O/${TAG}_c3_batch8.err
 # the other two engines on the same workload: IEEE half (the reference demo's own "16-mixed") and the exact-f32 parity engine (priced
 # against the 157 TF f32-input MFMA peak)
-python bench.py --precision 16-mixed --steps 20 --warmup 5 --no-cpu-baseline > $O/${TAG}_c3_f16_bench_line.json 2> $O/${TAG}_c3_f16.err
-python bench.py --precision 32-true --steps 3 --warmup 1 --no-cpu-baseline > $O/${TAG}_c3_f32_bench_line.json 2> $O/${TAG}_c3_f32.err
+python bench.py --full --precision 16-mixed --steps 20 --warmup 5 --no-cpu-baseline > $O/${TAG}_c3_f16_bench_line.json 2> $O/${TAG}_c3_f16.err
+python bench.py --full --precision 32-true --steps 3 --warmup 1 --no-cpu-baseline > $O/${TAG}_c3_f32_bench_line.json 2> $O/${TAG}_c3_f32.err
 python tools/prof_detail.py c3 5 > $O/${TAG}_c3_per_shape_event_profile.txt 2>/dev/null
 python tools/prof_detail.py c2 10 > $O/${TAG}_c2_per_shape_event_profile.txt 2>/dev/null
 cd /tmp
