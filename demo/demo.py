@@ -1,9 +1,11 @@
 """The generic-video part of the reference's demo (demo/demo.py:80-112) on the MI355X engine: VideoDataset ->
-DataLoader(batch_size=1) -> prepare_model(...).forward(batch, tasks).  Visualisation (l4p/utils/vis.py, viser) is out of
-scope; the outputs are reported (and optionally saved as .npz) instead.
+DataLoader(batch_size=1) -> prepare_model(...).forward(batch, tasks).  The 2D visualisations (l4p/utils/vis.py, viser) are out of
+scope; the outputs are reported (and optionally saved as .npz) instead.  --recon4d DIR adds the camray task and writes the 4D
+reconstruction of the reference's 4D sections (generate_4D_visualization, demo.py:116-258) as PLY files under DIR.
 
   python demo/demo.py --videos a.mp4 b.mp4 --ckpt weights/l4p_depth_flow_2d3dtrack_camray_dynseg_v1.ckpt   # needs mediapy
   python demo/demo.py --synthetic                      # no checkpoint / video files here: seeded weights + a seeded video
+  python demo/demo.py --synthetic --recon4d out/       # + 4D point clouds / track trails / frusta as PLY under out/
 
 With --synthetic the weights are the name-seeded random tensors of the test-suite (same 916-key state dict a checkpoint
 holds) and the "video" is l4p_amd.data.synthetic.synthetic_video: the point is the plumbing and the timing, not the pictures.
@@ -33,12 +35,17 @@ def main():
     ap.add_argument("--max-queries", type=int, default=128)
     ap.add_argument("--spacing", type=float, default=0.04, help="track_2d_querry_sampling_spacing (625 queries at 0.04)")
     ap.add_argument("--save", default=None, help="directory for <seq_name>.npz")
+    ap.add_argument("--recon4d", default=None, metavar="DIR",
+                    help="also run the camray task and write each video's 4D reconstruction (world point clouds, 3D track trails, "
+                         "camera frusta as PLY; l4p_amd.utils.recon4d.generate_4D_visualization) under DIR")
     ap.add_argument("--precision", default="16-mixed",
                     help="engine: 16-mixed (the reference demo's own, IEEE half; default) | bf16 (what bench.py measures) | 32-true")
     args = ap.parse_args()
 
     precision, accelerator = args.precision, "gpu"  # demo.py:22-23 hard-codes "16-mixed"
     tasks = ["depth", "flow_2d_backward", "dyn_mask", "track_2d"]  # demo.py:82,99
+    if args.recon4d:
+        tasks.append("camray")  # the reference's 4D sections (demo.py:116-258) add it
     frames = None
     if args.synthetic:
         from l4p_amd.weights import ModelCfg, seeded_state_dict
@@ -75,6 +82,30 @@ def main():
             os.makedirs(args.save, exist_ok=True)
             np.savez_compressed(os.path.join(args.save, os.path.splitext(batch["seq_name"][0])[0] + ".npz"),
                                 **{k: v.float().cpu().numpy() for k, v in out.items() if torch.is_tensor(v)})
+        if args.recon4d:
+            recon_4d(batch, out, tasks, args.recon4d)
+
+
+def recon_4d(batch, out, tasks, out_dir):
+    """generate_4D_visualization split into its GPU part and its file writing, each timed on its own.  (With --synthetic the
+    seeded weights give an arbitrary, possibly ill-conditioned K: the files are written, the geometry means nothing.)"""
+    from l4p_amd.utils import recon4d
+
+    T, H, W = batch["rgb_b3thw"].shape[2:]
+    seq = batch["seq_name"][0]
+    path = os.path.join(out_dir, seq)
+    os.makedirs(path, exist_ok=True)
+    batch["intrinsics_b44t"] = out["traj3d_intrinsics_est_b16t"].reshape(1, 4, 4, T)  # vis.py:126-127
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    rec = recon4d.reconstruct_4d(batch, out, tasks)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    recon4d.write_4d_files(rec, seq, path, T, H * W, "track_2d" in tasks)
+    t2 = time.perf_counter()
+    n = rec["points"].shape[0] + rec.get("track_xyz", rec["points"][:0]).shape[0]
+    print(f"  4D: {T} frames, {n / 1e6:.2f} M points, scale {float(rec.get('scale', torch.ones(1))[0]):.4g}; "
+          f"GPU reconstruction {(t1 - t0) * 1e3:.1f} ms, PLY writing {(t2 - t1) * 1e3:.0f} ms -> {path}")
 
 
 if __name__ == "__main__":

@@ -43,7 +43,8 @@ typedef void* l4p_stream; /* hipStream_t */
 typedef struct l4p_engine l4p_engine;
 
 const char* l4p_last_error(void);
-int l4p_abi_version(void); /* 9: l4p_similarity_prefix, knobs attn64 / probe_kernels; 8: l4p_gemm_desc.ups_hi / ups_wi; 7: L4P_F16; 6: l4p_set_knob / l4p_get_knob; 5: l4p_layernorm_res(out_stats), l4p_layernorm_chain, l4p_stream_create_cu_mask; 4: l4p_gemm_desc.o_gs, l4p_i2t_delta,
+int l4p_abi_version(void); /* 11: 4D reconstruction (l4p_recon_cameras, l4p_point_map, l4p_track_point_map, l4p_recon_track_prep,
+                              * l4p_recon_track_scale, l4p_recon_trails); 9: l4p_similarity_prefix, knobs attn64 / probe_kernels; 8: l4p_gemm_desc.ups_hi / ups_wi; 7: L4P_F16; 6: l4p_set_knob / l4p_get_knob; 5: l4p_layernorm_res(out_stats), l4p_layernorm_chain, l4p_stream_create_cu_mask; 4: l4p_gemm_desc.o_gs, l4p_i2t_delta,
                               * l4p_t2i_probs, l4p_t2i_context; 3: l4p_gemm_desc.w_gr / w_gs / b_gs, l4p_i2t_probs,
                               * l4p_t2i_attn_scores, l4p_split_hilo, l4p_transpose_pad */
 
@@ -328,6 +329,53 @@ int l4p_similarity_apply(l4p_stream stream, const float* sim, float* pose, int T
  * the scale after each product).  The sharded long-video path's seam-local exchange (reference loop
  * dense_heads.py:444-467, which aligns every window to the accumulated buffer one after the other). */
 int l4p_similarity_prefix(l4p_stream stream, const float* rel, float* out, int n, int B);
+
+/* ------------------------------------------------------------------------------------------------
+ * 4D reconstruction (generate_4D_visualization, l4p/utils/vis.py:107-221, traj3d branch): world point clouds of every pixel,
+ * camera frusta and 3D track trails of one clip (B = 1), from the depth, camray (traj3d) and track_2d outputs.  Matrices are
+ * float [16][T] (the b16t / b44t layout of one clip: element (i, j) of frame t at (i * 4 + j) * T + t).  All arithmetic f32,
+ * f64 where the reference computes in numpy float64 (frustum vertices, trail interpolation, colour normalisation).
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Cameras (vis.py:138-141; get_cam_T_ref geometry_utils.py:128-143; generate_video_camera_trajectory vis.py:621-641 with
+ * create_camera_frustum vis.py:529-618), A [B][16][T]: a_is_pose = 1: A = traj3d_est_b16t and cam_T_world_t = A_t^-1;
+ * a_is_pose = 0: A = cam_T_world.  cam_T_ref [B][16][T] = cam_T_world_t cam_T_world_ref^-1, world_T_cam [B][16][T] =
+ * cam_T_ref^-1, frustum [B][T][8][3] = world_T_cam applied to the frustum's camera-frame vertices (height 2 near tan_half_fov at
+ * z = near, 2 far tan_half_fov at z = far, aspect 1).  world_T_cam and frustum may be NULL. */
+int l4p_recon_cameras(l4p_stream stream, const float* A, int B, int T, int ref, int a_is_pose, double tan_half_fov, double near_d,
+                      double far_d, float* cam_T_ref, float* world_T_cam, float* frustum);
+/* Dense point map (generate_point_map, geometry_utils.py:13-53; every pixel, no filtering): depth [B][T][H][W], K and P
+ * (world_T_cam) [B][16][T]; component c of point (b, t, pixel q) goes to xyz[b * bs + (t * H * W + q) * ps + c * cs]
+ * (ps = 3, cs = 1: [T H W][3]; ps = 1, cs = T H W, bs = 3 T H W: b3thw).  Optional colour (vis.py:143, B = 1 only; rgb_u8 NULL
+ * skips it): rgb [3][T][H][W] * std[c] + mean[c] -> rgb_u8 [T H W][3] as min(255, max(0, c * 255)) truncated. */
+int l4p_point_map(l4p_stream stream, const float* depth, const float* K, const float* P, int B, int T, int H, int W, float* xyz,
+                  long long ps, long long cs, long long bs, const float* rgb, const float* mean, const float* stdv,
+                  unsigned char* rgb_u8);
+/* 3D track point map (generate_3d_track_point_map + unproject_2d_track_to_3d, geometry_utils.py:56-106): traj [B][N][2][T],
+ * depth [B][N][T] (times scale[0] when scale is not NULL, vis.py:169), K, P [B][16][T] -> out [B][N][3][T]; row i holds track
+ * order[b * N + i] when order is not NULL (the height sort, vis.py:722-727). */
+int l4p_track_point_map(l4p_stream stream, const float* traj, const float* depth, const float* K, const float* P,
+                        const float* scale, const int* order, int B, int N, int T, float* out);
+/* Track preparation (vis.py:146-169, 722-727, 745): order [N] = stable argsort of the y at frame 0 (ties to the lower index);
+ * per frame t and sorted track i: visible = sigmoid(vis_logit) > vis_thr; the depth map dmap [T][H][W] sampled as
+ * grid_sample(mode="nearest", align_corners=False) after the reference's (W - 1), (H - 1) normalisation (0 outside the image);
+ * ratios [T][N] = sample / depth for visible pairs (invisible ones hold the largest key of l4p_select_rank); flag [1] != 0 when a
+ * visible ratio is NaN; slot [T][N] = rank among the frame's visible tracks or -1; counts [T] visible tracks per frame;
+ * off [T + 2]: off[t] = first trail point of frame t (points per visible track: 1 at t = 0, seg * min(t, trail) after),
+ * off[T] = all trail points, off[T + 1] = all visible pairs.  traj [N][2][T], vis_logit and depth [N][T]. */
+int l4p_recon_track_prep(l4p_stream stream, const float* traj, const float* vis_logit, const float* depth, const float* dmap,
+                         int N, int T, int H, int W, float vis_thr, int trail, int seg, int* order, int* slot, float* ratios,
+                         int* flag, int* counts, long long* off);
+/* scale[0] = torch.median of the nvis visible ratios (vis.py:167, the lower median: l4p_select_rank of rank (nvis - 1) / 2 over
+ * the n = N T values of l4p_recon_track_prep), NaN when flag[0] != 0 or nvis = 0 (then no select is launched).
+ * ws >= L4P_QUANTILE_WS_UINTS uints, sel: one float of scratch. */
+int l4p_recon_track_scale(l4p_stream stream, const float* ratios, long long n, long long nvis, const int* flag, unsigned* ws,
+                          float* sel, float* scale);
+/* Trails (generate_3d_track_point_clouds, vis.py:738-766, tracks_leave_trace = trail, linspace(0, 1, seg)): X [N][3][T] world
+ * track points in sorted order (l4p_track_point_map with order), slot / off from l4p_recon_track_prep, lut [256][3] uchar hsv
+ * colours -> xyz [total][3], rgb [total][3], total = off[T].  total = 0 launches nothing. */
+int l4p_recon_trails(l4p_stream stream, const float* X, const int* slot, const long long* off, const unsigned char* lut, int N,
+                     int T, int trail, int seg, long long total, float* xyz, unsigned char* rgb);
 
 /* ------------------------------------------------------------------------------------------------
  * SAM-style point tracker (sparse_heads.py, sam/{prompt_encoder,transformer,mask_decoder}.py).

@@ -119,6 +119,12 @@ SIGNATURES = {
     "l4p_similarity_ransac": (_I, [_VP, _VP, _VP, _I, _VP, _F, _I, _I, C.c_uint, _VP, _VP]),
     "l4p_similarity_apply": (_I, [_VP, _VP, _VP, _I, _VP, _LL]),
     "l4p_similarity_prefix": (_I, [_VP, _VP, _VP, _I, _I]),
+    "l4p_recon_cameras": (_I, [_VP, _VP, _I, _I, _I, _I, C.c_double, C.c_double, C.c_double, _VP, _VP, _VP]),
+    "l4p_point_map": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP, _LL, _LL, _LL, _VP, _VP, _VP, _VP]),
+    "l4p_track_point_map": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP]),
+    "l4p_recon_track_prep": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _F, _I, _I, _VP, _VP, _VP, _VP, _VP, _VP]),
+    "l4p_recon_track_scale": (_I, [_VP, _VP, _LL, _LL, _VP, _VP, _VP, _VP]),
+    "l4p_recon_trails": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _LL, _VP, _VP]),
     "l4p_layernorm_ex": (_I, [_VP, _I, _VP, _VP, _VP, _F, _VP, _VP, _I, _I, _VP, _I, _VP, _I]),
     "l4p_gemm_group": (_I, [_VP, _I, _VP, _I]),
     "l4p_layernorm_res": (_I, [_VP, _I, _VP, _I, _VP, _VP, _VP, _F, _VP, _VP, _I, _I, _VP, _I, _VP, _VP, _I, _I, _VP]),

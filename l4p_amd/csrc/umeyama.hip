@@ -4,6 +4,7 @@
 // this is a deterministic counter-based-RNG re-statement of the same estimator, validated against synthetic
 // ground truth (tests/test_umeyama_gpu.py), not against the reference ("parity unpinned").
 #include "common.hpp"
+#include "unproject.hpp"
 
 __device__ __forceinline__ unsigned hash_u32(unsigned x) {  // PCG-style integer hash (counter-based RNG)
     x = x * 747796405u + 2891336453u;
@@ -143,20 +144,12 @@ __global__ void pointmap_kernel(const float* __restrict__ depth, const float* __
     int pix = j * ratio + (int)(hash_u32(seed ^ (unsigned)j * 2654435761u) % (unsigned)ratio);
     if (pix >= H * W) pix = H * W - 1;
     const float x = (float)(pix % W), y = (float)(pix / W);
-    const float* k = K + f * 16;
-    // inverse of the upper-left 3x3 (general, as torch.inverse does)
-    const float a = k[0], b = k[1], c = k[2], d = k[4], e = k[5], g = k[6], h = k[8], l = k[9], m = k[10];
-    const float det = a * (e * m - g * l) - b * (d * m - g * h) + c * (d * l - e * h);
-    const float id = 1.f / det;
-    const float i00 = (e * m - g * l) * id, i01 = (c * l - b * m) * id, i02 = (b * g - c * e) * id;
-    const float i10 = (g * h - d * m) * id, i11 = (a * m - c * h) * id, i12 = (c * d - a * g) * id;
-    const float i20 = (d * l - e * h) * id, i21 = (b * h - a * l) * id, i22 = (a * e - b * d) * id;
     const float z = depth[(long long)f * H * W + pix];
-    const float cx = (i00 * x + i01 * y + i02) * z, cy = (i10 * x + i11 * y + i12) * z, cz = (i20 * x + i21 * y + i22) * z;
-    const float* p = P + f * 16;
-    out[i * 3 + 0] = p[0] * cx + p[1] * cy + p[2] * cz + p[3];
-    out[i * 3 + 1] = p[4] * cx + p[5] * cy + p[6] * cz + p[7];
-    out[i * 3 + 2] = p[8] * cx + p[9] * cy + p[10] * cz + p[11];
+    float ox, oy, oz;
+    unproject_pixel(K + f * 16, P + f * 16, 1, x, y, z, ox, oy, oz);
+    out[i * 3 + 0] = ox;
+    out[i * 3 + 1] = oy;
+    out[i * 3 + 2] = oz;
 }
 
 // -------------------------------------------------------------------------------------------------
