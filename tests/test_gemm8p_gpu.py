@@ -432,7 +432,8 @@ def test_conv3_halo_fused_upsample_equals_upsample_then_conv(dev, probe_kernels,
     """l4p_gemm_desc.ups_hi / ups_wi: the bilinear (align_corners) up-sampling in front of a 3x3x3 conv formed inside the LDS-halo
     kernel's loader (dpt_head.py:79-84: interpolate -> head conv) - equal, bit for bit, to l4p_upsample_trilinear followed by the
     conv on the stored volume: the loader reproduces that kernel's arithmetic and rounding.  Full-size head shape and a small,
-    non-square one with a fractional scale in both axes."""
+    non-square one with a fractional scale in both axes.
+    (The expected side, l4p_upsample_trilinear, is itself pinned against float64 by tests/test_small_kernels_gpu.py::test_upsample_vs_float64.)"""
     Cin, cout = 128, 128
     x, _ = as_mode(rnd((B, T, lo[0], lo[1], Cin), 400), MODE)
     w = rnd((cout, Cin, 3, 3, 3), 401, (27 * Cin) ** -0.5)
