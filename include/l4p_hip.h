@@ -43,8 +43,9 @@ typedef void* l4p_stream; /* hipStream_t */
 typedef struct l4p_engine l4p_engine;
 
 const char* l4p_last_error(void);
-int l4p_abi_version(void); /* 11: 4D reconstruction (l4p_recon_cameras, l4p_point_map, l4p_track_point_map, l4p_recon_track_prep,
-                              * l4p_recon_track_scale, l4p_recon_trails); 9: l4p_similarity_prefix, knobs attn64 / probe_kernels; 8: l4p_gemm_desc.ups_hi / ups_wi; 7: L4P_F16; 6: l4p_set_knob / l4p_get_knob; 5: l4p_layernorm_res(out_stats), l4p_layernorm_chain, l4p_stream_create_cu_mask; 4: l4p_gemm_desc.o_gs, l4p_i2t_delta,
+int l4p_abi_version(void); /* 12: every launcher switch is a knob; 11: 4D reconstruction (l4p_recon_cameras, l4p_point_map,
+                              * l4p_track_point_map, l4p_recon_track_prep, l4p_recon_track_scale, l4p_recon_trails);
+                              * 10: l4p_gemm_desc.kw_cols / kw_len, l4p_t2i_context(shared_from); 9: l4p_similarity_prefix, knobs attn64 / probe_kernels; 8: l4p_gemm_desc.ups_hi / ups_wi; 7: L4P_F16; 6: l4p_set_knob / l4p_get_knob; 5: l4p_layernorm_res(out_stats), l4p_layernorm_chain, l4p_stream_create_cu_mask; 4: l4p_gemm_desc.o_gs, l4p_i2t_delta,
                               * l4p_t2i_probs, l4p_t2i_context; 3: l4p_gemm_desc.w_gr / w_gs / b_gs, l4p_i2t_probs,
                               * l4p_t2i_attn_scores, l4p_split_hilo, l4p_transpose_pad */
 
@@ -82,6 +83,33 @@ int l4p_stream_destroy(l4p_stream stream);
  *   "readout_wide" (L4P_READOUT_WIDE, default 1): l4p_track_readout with at most 512 (track, frame) pairs runs 1024 threads per pair
  *                (the samples of 32 rows formed by all threads, then summed per column in the order of the 256-thread kernel:
  *                bit-identical; 58 -> ~20 us per launch on a rank's 8-track shard); 0 = the 256-thread kernel
+ *   "track_deep" (L4P_TRACK_DEEP, default 1): row-grouped GEMMs whose grid leaves CUs idle (the folded score products of a rank's
+ *                8-track shard) run four stages deep - the same sums in the same order; 0 = the two-stage form
+ * The tracker window (l4p_track_window_forward / l4p_track_window_workspace_bytes; read once per window - the workspace size follows them):
+ *   "track_fold_l0" (L4P_TRACK_FOLD_L0, default 1): a later window's layer 0 runs its token -> image attention in the folded form; 0 = projected form
+ *   "track_fold_t2i" (L4P_TRACK_FOLD_T2I, default 1): token -> image attention with the keys' projection folded into the tokens; 0 = every key row projected
+ *   "track_fold_t2i_v" (L4P_TRACK_FOLD_T2I_V, default 1): ... and the value projection too (l4p_t2i_probs / l4p_t2i_context); 0 = the projected values + l4p_t2i_attn_scores
+ *   "track_kwin" (L4P_TRACK_KWIN, default 1): the folded weights' products walk only the k-tiles of a tile's head (l4p_gemm_desc.kw_cols: bit-identical); 0 = all k-tiles
+ *   "track_ln_chain" (L4P_TRACK_LN_CHAIN, default 1): chained key LayerNorm in a first window (l4p_layernorm_chain); 0 keeps the float key master
+ *   "track_fold_i2t" (L4P_TRACK_FOLD_I2T, default 1): image -> token attention folded into the 6 prompt tokens of each track; 0 = i2t.q / i2t.out over every image token
+ *   "track_fold_pair" (L4P_TRACK_FOLD_PAIR, default 0): 1 = K' of the folded image -> token scores as a PAIR of bf16 matrices (l4p_split_hilo; measured: changes nothing)
+ *   "track_delta_kernel" (L4P_TRACK_DELTA_KERNEL, default 1): delta = P x V' + b_out by its own streaming kernel (l4p_i2t_delta, bit-identical); 0 = the row-grouped GEMM
+ * The GEMM launchers (A/B and tuning aids):
+ *   "gemm_persist" (L4P_GEMM_PERSIST, default 1): only in a -DGEMM_8P_PERSIST_EXPERIMENT build: 0 = the plain launch of the 8-phase kernel
+ *   "skinny_max_m" (L4P_SKINNY_MAX_M, default 128): most rows the one-wave kernel of "gemm_skinny" takes
+ *   "gemm_deep"  (L4P_GEMM_DEEP, default 1): small problems (at most one workgroup per CU, K >= 384) on the four-stage 128x64 kernel; 0 = the two-deep ring
+ *   "gemm_group" (L4P_GEMM_GROUP, default 1): l4p_gemm_group runs independent projections as one launch; 0 = one launch each
+ *   "epi_generic" (L4P_EPI_GENERIC, default 0): 1 = the generic epilogue instead of the lean ones (l4p_gemm_desc.tuning bit 0)
+ *   "gemm_variant" (L4P_GEMM_VARIANT, default 0): 1 = never use the 8-phase kernel, 10 = always, 3 = 128x64 tiles
+ *   "gemm_t192"  (L4P_GEMM_T192, default 1): 256 x 192 tiles of the 8-phase kernel where they quantise better on the 256 CUs; 0 = 256 x 256
+ * Attention, up-sampling, the encoder:
+ *   "attn_persist" (L4P_ATTN_PERSIST, default 1): the persistent form of the 16-bit attention kernel where it applies; 0 = one workgroup per tile
+ *   "attn_variant" (L4P_ATTN_VARIANT, default 0): tuning aid: 1 = compiler-scheduled body, 2 = no query split
+ *   "ups_ipt"    (L4P_UPS_IPT, default 2) / "ups_nt" (L4P_UPS_NT, default 1): l4p_upsample_trilinear: items per thread / the 16-bit form with
+ *                non-temporal stores (0 = plain stores)
+ *   "fc2_splitk8" (L4P_FC2_SPLITK8, default -1): split-K of the encoder's MLP-out projection: -1 = chosen by tile count, 0 = the 2-slice form, n = n slices
+ *   "enc_defer_res" (L4P_ENC_DEFER_RES, default 1) / "enc_sk_in_ln" (L4P_ENC_SK_IN_LN, default 1): the 16-bit encoder defers a block's residual
+ *                sum to the LayerNorm that follows (0 = the fused-epilogue form) / that LayerNorm also sums the split-K partials (0 = finish pass)
  *   "probe_kernels" (read-only): 1 when the library was built with PROBES=1 and contains the measured-and-not-adopted kernels the knobs
  *                "gemm_4w" and "conv_ups" select; in the shipped build (0) those two knobs stay 0 and setting them is an error.
  * l4p_set_knob returns L4P_E_INVALID for an unknown name; l4p_get_knob returns the current value (or -1). */

@@ -14,6 +14,8 @@ L4P_BF16 = 0
 L4P_F32 = 1
 L4P_F16 = 2  # IEEE half storage / f16 MFMA: the arithmetic class of the reference's "16-mixed" (fp16 autocast)
 
+ABI_VERSION = 12  # what l4p_abi_version() of the library this binding was written against returns (include/l4p_hip.h)
+
 EPI_DENSE, EPI_QKV, EPI_CONVT, EPI_MASKDOT = 0, 1, 2, 3
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
 
@@ -190,6 +192,10 @@ def load() -> C.CDLL:
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args
+    have = int(lib.l4p_abi_version())
+    if have != ABI_VERSION:
+        raise L4PHipError(f"{LIB_PATH} reports ABI version {have}, this package binds version {ABI_VERSION}: "
+                          "stale library - rebuild it with `make -C l4p_amd/csrc`")
     _lib = lib
     return lib
 
@@ -211,9 +217,14 @@ def kernel_tree_hash() -> str:
     return h.hexdigest()[:16]
 
 
+knob_epoch = 0  # bumped by set_knob: what was derived from the knobs (Engine's tracker workspace sizes) is stale when it moved
+
+
 def set_knob(name: str, value: int) -> None:
-    """Dispatch knob of the native launchers (include/l4p_hip.h: "conv_halo", "gemm_4w")."""
+    """Dispatch knob of the native launchers (include/l4p_hip.h: "conv_halo", "gemm_4w", "track_fold_i2t", ...)."""
+    global knob_epoch
     check(load().l4p_set_knob(name.encode(), int(value)), f"l4p_set_knob({name})")
+    knob_epoch += 1
 
 
 def check(rc: int, what: str = "") -> None:

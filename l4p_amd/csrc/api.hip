@@ -29,7 +29,7 @@ int launch_layernorm_res(int dtype, const float* x, int x_mod, const void* delta
 extern "C" {
 
 const char* l4p_last_error(void) { return g_err; }
-int l4p_abi_version(void) { return 11; }
+int l4p_abi_version(void) { return 12; }
 
 // A HIP stream whose kernels run on CUs [first_cu, first_cu + n_cus) only (hipExtStreamCreateWithCUMask): the sharded long-video path
 // gives the tracker's latency-bound kernel chain a slice of the chip of its own, beside the chip-filling decoders on the rest.
@@ -180,7 +180,7 @@ static int enc_fc2_splitk(const l4p_engine* e, size_t M) {
     const l4p_encoder_cfg& c = e->enc;
     const size_t tiles = ((M + 127) / 128) * (((size_t)c.dim + 63) / 64);
     if (!(is16(e->dtype) && tiles < 512 && c.mlp_hidden >= 4096)) return 1;
-    static const int env8 = getenv("L4P_FC2_SPLITK8") ? atoi(getenv("L4P_FC2_SPLITK8")) : -1;  // (A/B aid: 0 = the 2-slice form, n = n slices)
+    const int env8 = knob(KNOB_FC2_SPLITK8);  // (A/B aid: 0 = the 2-slice form, n = n slices)
     const bool no8 = env8 == 0;
     const size_t t8 = ((M + 255) / 256) * (((size_t)c.dim + 255) / 256);
     const int sk8 = env8 > 1 ? env8 : (t8 > 0 ? (int)(200 / t8) : 0);  // (48 tiles: 4 slices 72.0 us, 5 slices 73.4, 3 slices 77.7; 2 slices of 128x128 tiles 76.1)
@@ -318,10 +318,10 @@ int l4p_encoder_forward(l4p_engine* e, l4p_stream stream_, const float* rgb, int
     // that follows, which reads x anyway (l4p_layernorm_res: y = LN(x + delta), x updated in place).  The projection leaves
     // bias + product in the engine dtype, which is what the reference's autocast linear returns before the float sum.
     // L4P_ENC_DEFER_RES=0: the fused-epilogue form (A/B aid).  The float engine keeps the fused form.
-    static const int defer_env = getenv("L4P_ENC_DEFER_RES") ? atoi(getenv("L4P_ENC_DEFER_RES")) : 1;
+    const int defer_env = knob(KNOB_ENC_DEFER_RES);
     const bool defer = is16(dt) && defer_env != 0 && C % 4 == 0 && C <= 1536;
     void* const delta = w.qk;  // [M][C] engine dtype, in the q / k slot (free between the attention and the next QKV projection)
-    static const int sk_in_ln = getenv("L4P_ENC_SK_IN_LN") ? atoi(getenv("L4P_ENC_SK_IN_LN")) : 1;  // (0: finish pass, A/B aid)
+    const int sk_in_ln = knob(KNOB_ENC_SK_IN_LN);  // (0: finish pass, A/B aid)
     bool pending = false;
     int pending_sk = 0;
     const float* pending_bias = nullptr;

@@ -2,11 +2,14 @@
 // (VideoMAETrack2DSamHead.forward / forward_single_batch, sparse_heads.py:497-667; PromptEncoder prompt_encoder.py:67-121;
 // TwoWayTransformer sam/transformer.py:67-111,156-187; MaskDecoder.predict_masks mask_decoder.py:101-141; memory tokens
 // sparse_heads.py:406-448,660-665) as ONE native call: ~125 kernel launches issued back to back from C++ on the caller's
-// stream, intermediates bump-allocated from a caller-provided workspace.  Same kernels, same order, same arguments as the
-// Python composition l4p_amd/models/task_heads/sparse_heads.py:_window (which remains as the readable statement of the
-// graph, selectable with L4P_TRACK_PYTHON=1, and is asserted bit-identical in tests/test_track_gpu.py).  What it buys: the
+// stream, intermediates bump-allocated from a caller-provided workspace.  This file is the one statement of the window's graph:
+// its dispatch switches are knobs (prof.hip: L4P_TRACK_* defaults, l4p_set_knob), read once per window at the top of run(), and the
+// tests flip them on this code (tests/test_track_gpu.py, tests/test_full_model_gpu.py).  What the single call buys: the
 // host issues one call per clip and window instead of ~125 ctypes calls with their tensor allocations — with 8 ranks
 // sharing one host's cores that is what keeps the step from becoming launch-bound.
+// The workspace size (l4p_track_window_workspace_bytes) is a dry run of the same function and so depends on the tracker knobs; a
+// workspace that is too small for the current setting is refused (Stack::take returns null, TW::alloc sets L4P_E_INVALID and every
+// launch is behind !rc), never overrun.
 #include <stdlib.h>
 #include <string.h>
 
@@ -173,7 +176,9 @@ int run(TW& c, const l4p_track_cfg& g, const float* enc_last, float* hist, const
     // (the per-(track, head) attention kernel on projected keys / values is 120 us per window whatever the number of tracks, and the two
     // projections of N x P key rows go with it: 8 tracks 240 -> 110 us).  A window evaluated out of context (0) keeps the projected
     // form, which the first window's shared-key shortcut equals bit for bit.  L4P_TRACK_FOLD_L0=0: A/B aid.
-    static const bool fold_l0_env = !(getenv("L4P_TRACK_FOLD_L0") && atoi(getenv("L4P_TRACK_FOLD_L0")) == 0);
+    const bool fold_l0_env = knob(KNOB_TRACK_FOLD_L0) != 0;
+    // (the switches of the image -> token block, read once per window like the others: see that block)
+    const bool fold_env = knob(KNOB_TRACK_FOLD_I2T) != 0, pair_env = knob(KNOB_TRACK_FOLD_PAIR) == 1, delta_env = knob(KNOB_TRACK_DELTA_KERNEL) != 0;
     const bool fold_l0 = fold_l0_env && (hist_uniform == 2 || hist_uniform == 4);
     if (hist_uniform == 2 || hist_uniform == 4) hist_uniform = 0;
     // projection of per-track keys x [N*P][Cc] whose second temporal half is common to all tracks: the first halves of all
@@ -238,7 +243,7 @@ int run(TW& c, const l4p_track_cfg& g, const float* enc_last, float* hist, const
     // its keys): Q' = q_tok x kfold^T [N][HT][C], scores = kP x Q'^T (row-grouped weights), softmax over the P keys and P.V in
     // l4p_t2i_attn_scores.  The [N * P, C/2] key projection (2 * P * C * C/2 FLOP per track, 4.06 GF) and its tensor disappear; the
     // value projection: see fold_v below.
-    static const bool fold_t2i_env = !(getenv("L4P_TRACK_FOLD_T2I") && atoi(getenv("L4P_TRACK_FOLD_T2I")) == 0);
+    const bool fold_t2i_env = knob(KNOB_TRACK_FOLD_T2I) != 0;
     const int HTk = 6 * g.sam_heads;
     const bool fold_t2i_ok = fold_t2i_env && P % 128 == 0 && HTk <= 64;
     // ... and the VALUE projection too (l4p_t2i_context: out = (probs x keys) Wv_h^T + bv_h): softmax to probs [N][P][HT]
@@ -246,12 +251,12 @@ int run(TW& c, const l4p_track_cfg& g, const float* enc_last, float* hist, const
     // and the 48 context rows of each track through their head's block of W_v (row-grouped weights over head-major rows, every group
     // writing its own column block of `ta`: o_gs).  Another 4.06 GF and a [P, C/2] tensor per track gone.  L4P_TRACK_FOLD_T2I_V=0:
     // the projected values + l4p_t2i_attn_scores.
-    static const bool fold_v_env = !(getenv("L4P_TRACK_FOLD_T2I_V") && atoi(getenv("L4P_TRACK_FOLD_T2I_V")) == 0);
+    const bool fold_v_env = knob(KNOB_TRACK_FOLD_T2I_V) != 0;
     const bool fold_v = fold_t2i_ok && fold_v_env && HTk == 48 && Cc % 128 == 0 && (Dh / g.sam_heads) % 8 == 0 && P % 32 == 0 && P >= 96 && P <= 4096;
     const long long RgT = (6ll * N + 127) / 128 * 128;  // rows of a head group of the context (and of `ta`, whose rows past 6 N are scratch)
     // the folded weights are block-structured (packing.py fold_i2t / fold_t2i: head h's C columns meet head h's C/2/heads inputs only):
     // their products walk only the k-tiles of a tile's head (l4p_gemm_desc.kw_cols: bit-identical, a quarter of the weight bytes)
-    static const bool kwin_env = !(getenv("L4P_TRACK_KWIN") && atoi(getenv("L4P_TRACK_KWIN")) == 0);
+    const bool kwin_env = knob(KNOB_TRACK_KWIN) != 0;
     const int kw_cols = kwin_env && Cc % 128 == 0 ? Cc : 0, kw_len = Dh / g.sam_heads;
     // hs: rows [P/2, P) of keysP / keysT exist for track 0 only (a later window's layer 0): the scores of the two halves are two
     // row-mapped launches, the context product reads those rows from track 0, the projected values (fold_v off) are formed once and copied
@@ -302,7 +307,7 @@ int run(TW& c, const l4p_track_cfg& g, const float* enc_last, float* hist, const
         }
     };
     // chained key LayerNorm (see the image -> token block below): L4P_TRACK_LN_CHAIN=0 keeps the float key master
-    static const bool chain_env = !(getenv("L4P_TRACK_LN_CHAIN") && atoi(getenv("L4P_TRACK_LN_CHAIN")) == 0);
+    const bool chain_env = knob(KNOB_TRACK_LN_CHAIN) != 0;
     const bool may_chain = chain_env && start_shared && g.sam_depth >= 2 && Cc <= 1536;
     float* chain_stats = may_chain ? c.f32(NP, 2) : nullptr;
     // (a third layer would need the chained layer's float result: with the master's storage holding layer 0's update it gets its own)
@@ -380,7 +385,6 @@ int run(TW& c, const l4p_track_cfg& g, const float* enc_last, float* hist, const
             // V' = v_tok x ofold^T [N][HT][C] (three small GEMMs), V'^T [N][C][HTp].  Image side: scores = kP x K'^T + c (row-grouped
             // weights: a track's rows meet that track's K'), softmax over the tokens of each head, delta = P x V' + b_out.
             // Per 64 tracks: 0.37 GB read + 0.37 GB written and 35 GFLOP, where the projections moved 1.3 GB and 520 GFLOP.
-            static const bool fold_env = !(getenv("L4P_TRACK_FOLD_I2T") && atoi(getenv("L4P_TRACK_FOLD_I2T")) == 0);
             // (keys still common to all tracks: the same GEMM on row m % P of the common set; later windows, layer 0: the second
             //  temporal half of every track is track 0's - two launches over the half blocks, row-mapped like proj_half_shared)
             const bool hs0 = half_shared && l == 0;
@@ -392,7 +396,6 @@ int run(TW& c, const l4p_track_cfg& g, const float* enc_last, float* hist, const
                 // MEASURED (tools/probes/fold_precision.py, per-track distance of the bf16 engine from the f32 engine over 4 - 6 windows):
                 // with K' rounded ONCE to bf16 the folded form is already as close to f32 as the projected form (traj 3e-4, depth
                 // 6e-3 per track, both forms) - the pair changes nothing and is off (L4P_TRACK_FOLD_PAIR=1 turns it on).
-                static const bool pair_env = getenv("L4P_TRACK_FOLD_PAIR") && atoi(getenv("L4P_TRACK_FOLD_PAIR")) == 1;
                 const bool pair = pair_env && is16(c.dt);
                 const int NS = pair ? 2 * HT : HT;               // score columns
                 float* kf32 = pair ? c.f32(6ll * N, (int)KW) : nullptr;
@@ -431,7 +434,6 @@ int run(TW& c, const l4p_track_cfg& g, const float* enc_last, float* hist, const
                         c.rc = launch_gemm(c.dt, 0, p, c.st);
                     }
                     if (!c.rc) c.rc = launch_i2t_probs(c.dt, sc, NS, pair ? 1 : 0, cf, P, pr, HTp, NP, g.sam_heads, 6, c.st);
-                    static const bool delta_env = !(getenv("L4P_TRACK_DELTA_KERNEL") && atoi(getenv("L4P_TRACK_DELTA_KERNEL")) == 0);
                     if (!c.rc && delta_env && is16(c.dt) && HTp == 64 && Cc % 128 == 0 && P % 16 == 0) {
                         // (its own streaming kernel, bit-identical to the GEMM below: see i2t_delta_kernel)
                         c.rc = launch_i2t_delta(c.dt, pr, vt, c.Wf(lo + "i2t.out.b"), delta, N, P, Cc, HTp, c.st);
@@ -635,9 +637,8 @@ int l4p_track_window_forward(l4p_engine* e, l4p_stream stream, const l4p_track_c
     c.st = (hipStream_t)stream;
     c.dt = e->dtype;
     c.es = esize_of(e->dtype);
-    const size_t mis = (size_t)((uintptr_t)workspace & 255);
-    char* base = (char*)workspace + (mis ? 256 - mis : 0);
-    c.ws = Stack{base, 0, ws_bytes - (mis ? 256 - mis : 0), 0, false};
+    const size_t pad = (size_t)(-(uintptr_t)workspace & 255);  // to the next 256-byte boundary
+    c.ws = Stack{(char*)workspace + pad, 0, ws_bytes > pad ? ws_bytes - pad : 0, 0, false};
     return run(c, *cfg, enc_last, hist, q_off, labels, pfeat, plabel, N, need_history, hist_uniform, traj, vis, depth, new_pfeat);
 }
 

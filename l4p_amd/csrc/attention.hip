@@ -700,7 +700,7 @@ static int launch_attn_t(const void* q, const void* kt, const void* vt, void* ou
     const int ntiles = (S / (128 * QS)) * H * B;
     // query-split form: persistent workgroups (one 8-wave workgroup per CU) that walk the tiles with the next tile's operands
     // prefetched across the seam; the Q staging buffer sits behind the tile rings
-    static const int persist_env = getenv("L4P_ATTN_PERSIST") ? atoi(getenv("L4P_ATTN_PERSIST")) : 1;
+    const int persist_env = knob(KNOB_ATTN_PERSIST);
     const bool persist = SPLIT == 1 && QS > 1 && persist_env && S / KVB >= 4 && (S / KVB) % 2 == 0;  // (the kernel's PERSIST)
     const int slots = 256;  // one 8-wave workgroup per CU (250 registers: two waves per SIMD)
     const int grid = persist && ntiles > slots ? slots : ntiles;
@@ -746,7 +746,7 @@ int launch_attention(int dtype, const void* q, const void* kt, const void* vt, v
     }
     // too few workgroups for two per CU (256 CUs): split the KV range over two wave groups inside each workgroup
     const bool split = (long long)(S / 128) * H * B < 512 && (S / 64) % 2 == 0;
-    static const int variant = getenv("L4P_ATTN_VARIANT") ? atoi(getenv("L4P_ATTN_VARIANT")) : 0;  // tuning aid: 1 = compiler-scheduled body
+    const int variant = knob(KNOB_ATTN_VARIANT);  // tuning aid: 1 = compiler-scheduled body
     // chip-filling 16-bit launches: one wave per SIMD, 64 query rows per wave (attention64.hip)
     if (is16(dtype) && variant == 0 && knob(KNOB_ATTN64) && S % 256 == 0 && (S / 64) % 2 == 0 && S / 64 >= 4 && (long long)(S / 256) * H * B >= 256)
         return launch_attention64(dtype, q, kt, vt, out, B, S, H, Dh, scale, stream);

@@ -161,7 +161,7 @@ int launch_upsample(int dtype, const void* x, void* y, int B, int Ti, int Hi, in
     const int lines = B * To * Ho, per_line = Wo * (C / 8);
     // two items per thread (fewer, longer workgroups: 2.55 -> 2.18 ms per c3 step) and non-temporal stores (the output,
     // up to 822 MB, is streamed to the next conv and never fits a cache: -> 2.02 ms); L4P_UPS_IPT / L4P_UPS_NT: tuning aids
-    static const int ipt = getenv("L4P_UPS_IPT") ? atoi(getenv("L4P_UPS_IPT")) : 2;
+    const int ipt = knob(KNOB_UPS_IPT);
     int gx = (per_line + 256 * ipt - 1) / (256 * ipt);
     gx = gx < 1 ? 1 : (gx > 64 ? 64 : gx);
     const dim3 grid(gx, lines < 65535 ? lines : 65535, (lines + 65534) / 65535);
@@ -176,7 +176,7 @@ int launch_upsample(int dtype, const void* x, void* y, int B, int Ti, int Hi, in
     if ((cvn & (cvn - 1)) == 0)
         for (cv_shift = 0; (1 << cv_shift) < cvn; ++cv_shift) {
         }
-    static const int nt = getenv("L4P_UPS_NT") ? atoi(getenv("L4P_UPS_NT")) : 1;
+    const int nt = knob(KNOB_UPS_NT);
     if (is16(dtype) && nt) L4P_WITH_T16(dtype, T16, hipLaunchKernelGGL((upsample_kernel<T16, true>), grid, dim3(256), 0, stream, (const T16*)x, (T16*)y, B, Ti,
                            Hi, Wi, To, Ho, Wo, C, align, st, sh, sw, cv_shift));
     else if (is16(dtype)) L4P_WITH_T16(dtype, T16, hipLaunchKernelGGL(upsample_kernel<T16>, grid, dim3(256), 0, stream, (const T16*)x, (T16*)y, B, Ti,

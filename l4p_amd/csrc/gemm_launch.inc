@@ -125,7 +125,7 @@ static int launch_8p(const GemmParams& p, hipStream_t stream) {
         // keeps ~270 scalars live where the plain kernel keeps ~70: the epilogue re-reads them from VGPR lanes (2 800 v_readlane in
         // the object code) and that costs more per tile than the hardware's workgroup launch + the exposed first round trip did.
         // Compiled only with -DGEMM_8P_PERSIST_EXPERIMENT (L4P_GEMM_PERSIST=0 then selects the plain launch).
-        static const int persist = getenv("L4P_GEMM_PERSIST") ? atoi(getenv("L4P_GEMM_PERSIST")) : 1;
+        const int persist = knob(KNOB_GEMM_PERSIST);
         const int cus = device_cu_count();
         if (persist && cus >= 8 && cus % 8 == 0 && ntm * ntn > cus)
             return launch_8p_form<MODE, WR, WC, SPLITK, TM, TN, true>(p, stream, cus);
@@ -216,7 +216,7 @@ int GEMM_FN(int mode, const GemmParams& p_in, hipStream_t stream);
 static bool gemm_is_skinny(const GemmParams& p) {
     // (tools/probes/skinny_m_sweep.py, N = 1408, K = 1408: 6.1 us against 13.9 us up to 64 rows, 9.7 against 14.2 at 96 - 128 rows - more than
     //  256 waves, two to a CU; beyond 512 blocks the staged kernel is as fast)
-    static const int max_m = getenv("L4P_SKINNY_MAX_M") ? atoi(getenv("L4P_SKINNY_MAX_M")) : 128;
+    const int max_m = knob(KNOB_SKINNY_MAX_M);
     return knob(KNOB_GEMM_SKINNY) && p.M >= 1 && p.M <= max_m && p.K >= 64 && p.K % 64 == 0 && p.lda % 8 == 0 && p.ldw % 8 == 0 && p.N % 8 == 0 &&
            p.w_gr == 0 && p.kw_cols == 0 && p.splitk <= 1 && !p.relu_in && p.epi == L4P_EPI_DENSE && !(p.tuning & 4) &&
            (long long)((p.M + 15) / 16) * ((p.N + 31) / 32) <= 512;  // (wider: every row block streams the weights again - measured
@@ -249,8 +249,8 @@ static bool gemm_is_small_deep(const GemmParams& p) {
     return !big && p.splitk <= 1 && !p.relu_in && t64 <= 256 && p.K >= 6 * 64 && !(p.tuning & 1) && p.w_gr == 0;
 }
 int GEMM_GROUP_FN(const GemmParams* p, int n, hipStream_t stream) {
-    static const int deep = getenv("L4P_GEMM_DEEP") ? atoi(getenv("L4P_GEMM_DEEP")) : 1;
-    static const int group = getenv("L4P_GEMM_GROUP") ? atoi(getenv("L4P_GEMM_GROUP")) : 1;
+    const int deep = knob(KNOB_GEMM_DEEP);
+    const int group = knob(KNOB_GEMM_GROUP);
     if (group && n >= 2 && n <= L4P_GEMM_GROUP_MAX) {  // all of them skinny: one launch of the one-wave kernel
         bool sk = true;
         long long waves = 0;
@@ -316,7 +316,7 @@ int GEMM_GROUP_FN(const GemmParams* p, int n, hipStream_t stream) {
 }
 #endif
 int GEMM_FN(int mode, const GemmParams& p_in, hipStream_t stream) {
-    static const int epi_generic = getenv("L4P_EPI_GENERIC") ? atoi(getenv("L4P_EPI_GENERIC")) : 0;
+    const int epi_generic = knob(KNOB_EPI_GENERIC);
     const bool maskdot_valu = p_in.epi == L4P_EPI_MASKDOT && !knob(KNOB_MASKDOT_MFMA);  // (A/B and parity aid: the all-VALU form)
     if (!epi_generic && !maskdot_valu) return GEMM_FN_impl(mode, p_in, stream);
     GemmParams p = p_in;
@@ -364,7 +364,7 @@ static int GEMM_FN_impl(int mode, const GemmParams& p, hipStream_t stream) {
     // bandwidth (M = 8192, N = 256, K = 27648: 2.65 GB of tile loads in 250 us); 128x128 halves the bytes per FLOP
     // (250 -> 147 us, 77 -> 59 us, 133 -> 92 us on the c3 shapes).  The split count (splitk_for) assumes this.
     const bool big = (t128 >= 400 && !(t128 > 512 && t128 < 640)) || (p.splitk > 1 && p.N >= 256);
-    static const int variant = getenv("L4P_GEMM_VARIANT") ? atoi(getenv("L4P_GEMM_VARIANT")) : 0;
+    const int variant = knob(KNOB_GEMM_VARIANT);
 #ifdef GEMM_HAS_8P
     {
         // L4P_CONV_HALO=0: the implicit-GEMM forms for every conv (A/B aid)
@@ -391,7 +391,7 @@ static int GEMM_FN_impl(int mode, const GemmParams& p, hipStream_t stream) {
         const long long w8 = (long long)((p.M + 255) / 256) * ((p.N + 255) / 256) * p.splitk;
         // (256 x 192 tiles when they fill the chip better in that one round: the same projection is 64 tiles x 4 slices = 256
         //  workgroups; L4P_GEMM_T192=0: A/B aid)
-        static const int t192sk = getenv("L4P_GEMM_T192") ? atoi(getenv("L4P_GEMM_T192")) : 1;
+        const int t192sk = knob(KNOB_GEMM_T192);
         const long long w192 = (long long)((p.M + 255) / 256) * ((p.N + 191) / 192) * p.splitk;
         if (t192sk && w192 > w8 && w192 <= 256 && w8 >= 144 && p.K / p.splitk >= 512) return launch_8p<0, 4, 2, true, 4, 6>(p, stream);
         if (w8 >= 144 && w8 <= 256 && p.K / p.splitk >= 512) return launch_8p<0, 2, 4, true>(p, stream);
@@ -419,7 +419,7 @@ static int GEMM_FN_impl(int mode, const GemmParams& p, hipStream_t stream) {
 #endif
             // 256 x 192 tiles (wave tile 64 x 96) where they quantise better on the 256 CUs: rounds x outputs per tile
             // (the batch-4 encoder: out projection / MLP-out 192 tiles -> 256, QKV 576 -> 768; L4P_GEMM_T192=0: A/B aid)
-            static const int t192 = getenv("L4P_GEMM_T192") ? atoi(getenv("L4P_GEMM_T192")) : 1;
+            const int t192 = knob(KNOB_GEMM_T192);
             const long long n192 = (long long)((p.M + 255) / 256) * ((p.N + 191) / 192);
             const long long c256 = (t8 + 255) / 256 * 65536, c192 = (n192 + 255) / 256 * 49152;
             if (t192 && c192 < c256 && epilogue_is_lean_8p(p)) return launch_8p<0, 4, 2, false, 4, 6>(p, stream);
@@ -444,7 +444,7 @@ static int GEMM_FN_impl(int mode, const GemmParams& p, hipStream_t stream) {
         // k-tiles in flight (96 KB of LDS: irrelevant when the grid does not fill the chip anyway).  L4P_GEMM_DEEP=0: A/B aid.
         if (sizeof(GEMM_T) == 2 && !big && p.splitk <= 1) {
             const long long t64 = (long long)((p.M + 127) / 128) * ((p.N + 63) / 64);
-            static const int deep = getenv("L4P_GEMM_DEEP") ? atoi(getenv("L4P_GEMM_DEEP")) : 1;
+            const int deep = knob(KNOB_GEMM_DEEP);
             if (deep && t64 <= 256 && p.K >= 6 * 64) return launch_cfg<128, 64, 0, true, 4>(p, stream);
             // (between one and two rounds of 128 x 64 tiles - the batch-1 encoder's attention projection, 352 tiles: the four-stage form on
             //  128 x 128 tiles, one workgroup per CU, was measured at +0.2 % on configs[1] (1561 -> 1564 frames/s, two alternations): not kept)

@@ -28,6 +28,28 @@ const KnobDef kKnobs[KNOB_NUM] = {{"conv_halo", "L4P_CONV_HALO", 1}, {"gemm_4w",
                                    {"gemm_skinny", "L4P_GEMM_SKINNY", 1},
                                    {"readout_wide", "L4P_READOUT_WIDE", 1},
                                    {"track_deep", "L4P_TRACK_DEEP", 1},
+                                   {"track_fold_l0", "L4P_TRACK_FOLD_L0", 1},
+                                   {"track_fold_t2i", "L4P_TRACK_FOLD_T2I", 1},
+                                   {"track_fold_t2i_v", "L4P_TRACK_FOLD_T2I_V", 1},
+                                   {"track_kwin", "L4P_TRACK_KWIN", 1},
+                                   {"track_ln_chain", "L4P_TRACK_LN_CHAIN", 1},
+                                   {"track_fold_i2t", "L4P_TRACK_FOLD_I2T", 1},
+                                   {"track_fold_pair", "L4P_TRACK_FOLD_PAIR", 0},
+                                   {"track_delta_kernel", "L4P_TRACK_DELTA_KERNEL", 1},
+                                   {"gemm_persist", "L4P_GEMM_PERSIST", 1},
+                                   {"skinny_max_m", "L4P_SKINNY_MAX_M", 128},
+                                   {"gemm_deep", "L4P_GEMM_DEEP", 1},
+                                   {"gemm_group", "L4P_GEMM_GROUP", 1},
+                                   {"epi_generic", "L4P_EPI_GENERIC", 0},
+                                   {"gemm_variant", "L4P_GEMM_VARIANT", 0},
+                                   {"gemm_t192", "L4P_GEMM_T192", 1},
+                                   {"attn_persist", "L4P_ATTN_PERSIST", 1},
+                                   {"attn_variant", "L4P_ATTN_VARIANT", 0},
+                                   {"ups_ipt", "L4P_UPS_IPT", 2},
+                                   {"ups_nt", "L4P_UPS_NT", 1},
+                                   {"fc2_splitk8", "L4P_FC2_SPLITK8", -1},
+                                   {"enc_defer_res", "L4P_ENC_DEFER_RES", 1},
+                                   {"enc_sk_in_ln", "L4P_ENC_SK_IN_LN", 1},
                                    {"probe_kernels", "", 0}};
 std::atomic<int> g_knob[KNOB_NUM];
 std::once_flag g_knob_once;

@@ -21,7 +21,18 @@ enum ProfClass {
 };
 
 // Dispatch knobs (l4p_set_knob / l4p_get_knob, include/l4p_hip.h): environment default read once, run-time setter for the tests.
-enum Knob { KNOB_CONV_HALO = 0, KNOB_GEMM_4W, KNOB_MASKDOT_MFMA, KNOB_CONV_UPS, KNOB_LN_TRACKS, KNOB_LN_ROWS16, KNOB_ATTN64, KNOB_GEMM_SKINNY, KNOB_READOUT_WIDE, KNOB_TRACK_DEEP, KNOB_PROBE_KERNELS, KNOB_NUM };
+enum Knob {
+    KNOB_CONV_HALO = 0, KNOB_GEMM_4W, KNOB_MASKDOT_MFMA, KNOB_CONV_UPS, KNOB_LN_TRACKS, KNOB_LN_ROWS16, KNOB_ATTN64, KNOB_GEMM_SKINNY,
+    KNOB_READOUT_WIDE, KNOB_TRACK_DEEP,
+    // the tracker window (api_trackwin.hip)
+    KNOB_TRACK_FOLD_L0, KNOB_TRACK_FOLD_T2I, KNOB_TRACK_FOLD_T2I_V, KNOB_TRACK_KWIN, KNOB_TRACK_LN_CHAIN, KNOB_TRACK_FOLD_I2T,
+    KNOB_TRACK_FOLD_PAIR, KNOB_TRACK_DELTA_KERNEL,
+    // the GEMM launchers (gemm_launch.inc)
+    KNOB_GEMM_PERSIST, KNOB_SKINNY_MAX_M, KNOB_GEMM_DEEP, KNOB_GEMM_GROUP, KNOB_EPI_GENERIC, KNOB_GEMM_VARIANT, KNOB_GEMM_T192,
+    // attention.hip, dpt_ops.hip, api.hip
+    KNOB_ATTN_PERSIST, KNOB_ATTN_VARIANT, KNOB_UPS_IPT, KNOB_UPS_NT, KNOB_FC2_SPLITK8, KNOB_ENC_DEFER_RES, KNOB_ENC_SK_IN_LN,
+    KNOB_PROBE_KERNELS, KNOB_NUM
+};
 int knob(int id);
 
 void prof_begin(int cls, hipStream_t stream, const char* tag = nullptr);

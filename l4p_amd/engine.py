@@ -44,6 +44,7 @@ class Engine:
         self._dpt_ws: Dict[Tuple[str, int], torch.Tensor] = {}
         self._trk_ws: Dict[int, torch.Tensor] = {}
         self._trk_need: Dict[Tuple[int, int], int] = {}
+        self._trk_epoch = _lib.knob_epoch
         ec = EncoderCfg(dim=cfg.dim, depth=cfg.depth, heads=cfg.heads, head_dim=cfg.head_dim, mlp_hidden=cfg.mlp_hidden,
                         in_chans=cfg.in_chans, frames=cfg.frames, img_h=cfg.img, img_w=cfg.img, pt=cfg.patch[0],
                         ph=cfg.patch[1], pw=cfg.patch[2], patch_kp=int(weights.meta["patch_kp"]), ln_eps=cfg.ln_eps)
@@ -128,6 +129,9 @@ class Engine:
         # ONE workspace per slot, sized for the largest of the three history forms at the largest N seen (a clip's first
         # window runs hu = 1, its later ones hu = 2, a last chunk has fewer queries: keyed by shape, every forward freed and
         # re-allocated several hundred MB per clip); it only ever grows
+        if self._trk_epoch != _lib.knob_epoch:  # the size is a dry run of the window and follows the tracker knobs
+            self._trk_need.clear()
+            self._trk_epoch = _lib.knob_epoch
         need = self._trk_need.get((N, hu))
         if need is None:
             for h in (0, 1, 2, 4):

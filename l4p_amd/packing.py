@@ -175,7 +175,7 @@ def pack_track(pk: Packer, sd: Dict[str, torch.Tensor], c: ModelCfg, task: str =
 
     def fold_i2t(src: str, dst: str):
         """Image -> token attention with its image-side projections folded into the token side (sam/transformer.py:180-185,
-        223-245; used from sparse_heads._window / csrc/api_trackwin.hip once every track owns its keys):
+        223-245; used from csrc/api_trackwin.hip once every track owns its keys):
           scores[p, t, h] = scale * (kP[p] Wq^T + bq)_h . k_t,h  =  kP[p] . K'[t, h]  +  c[t, h]
           out[p]          = sum_{t,h} softmax_t(scores)[p, t, h] * (Wout_h v_t,h)  + bout  =  P[p] . V'  + bout
         K' = k_tok x qfold^T, c = k_tok x cfold^T, V' = v_tok x ofold^T are three small GEMMs on the 6 tokens of a track, with

@@ -536,13 +536,13 @@ def test_full_size_24_tracks_four_windows_integer_state(dev, full_sd, precision)
         assert_bf16_within_reference_drift(rep, "full_T40_track24", what="24 tracks", precision=precision)
 
 
-def test_folded_value_projection_equals_projected_values_at_full_size(dev, full_sd, monkeypatch):
+def test_folded_value_projection_equals_projected_values_at_full_size(dev, full_sd, knob):
     """The tracker at the FULL geometry (1408 channels, 8 heads of 88: where the value projection of the token -> image attentions is
     folded away - l4p_t2i_probs / l4p_t2i_context; the mini geometry's head dim 44 keeps the projected values) against
-    the projected form (L4P_TRACK_FOLD_T2I_V=0) over 3 windows (24 frames) with 8 tracks: the same function of the same weights.
+    the projected form (knob track_fold_t2i_v = 0) over 3 windows (24 frames) with 8 tracks: the same function of the same weights.
     f32 engine: equal to rounding (1e-4 of the maximum), values that mark invalid entries identical.  bf16 engine: each form as close
-    to the f32 engine as the other (mean distance of the tracks within 1.5x, worst track within 2x), and the native window call bit-identical to the Python composition
-    that the switch is read by."""
+    to the f32 engine as the other (mean distance of the tracks within 1.5x, worst track within 2x).  Both forms run through the native
+    window call (csrc/api_trackwin.hip), switched by its knob."""
     batch = make_batch(24, 8)
     keys = ["track_2d_traj_est_bn2t", "track_2d_vis_est_bn1t", "track_2d_depth_est_bn1t"]
     res = {}
@@ -550,18 +550,12 @@ def test_folded_value_projection_equals_projected_values_at_full_size(dev, full_
         m = build_model(os.path.join(ROOT, "configs", "model.yaml"), precision=precision)
         m.load_state_dict({"l4p_model." + k: v for k, v in full_sd.items()})
         with torch.no_grad():
-            monkeypatch.setenv("L4P_TRACK_PYTHON", "1")
-            monkeypatch.setenv("L4P_TRACK_FOLD_T2I_V", "1")
+            knob("track_fold_t2i_v", 1)
             a = m.forward({k: v.clone() for k, v in batch.items()}, ["track_2d"])
-            monkeypatch.setenv("L4P_TRACK_FOLD_T2I_V", "0")
+            knob("track_fold_t2i_v", 0)
             b = m.forward({k: v.clone() for k, v in batch.items()}, ["track_2d"])
-            monkeypatch.delenv("L4P_TRACK_PYTHON")
-            monkeypatch.delenv("L4P_TRACK_FOLD_T2I_V")
-            c = m.forward({k: v.clone() for k, v in batch.items()}, ["track_2d"])
         torch.cuda.synchronize()
         res[precision] = ({k: a[k].float().cpu() for k in keys}, {k: b[k].float().cpu() for k in keys})
-        for k in keys:
-            assert torch.equal(a[k], c[k]), (precision, k, "native vs Python composition", float((a[k] - c[k]).abs().max()))
         del m
 
     def per_track(x, y):
@@ -580,3 +574,28 @@ def test_folded_value_projection_equals_projected_values_at_full_size(dev, full_
         #  forms are compared on the tracks' mean and worst distance, not track by track)
         assert float(d_fold.mean()) <= 1.5 * float(d_proj.mean()) + 1e-4, (k, d_fold, d_proj)
         assert float(d_fold.max()) <= 2.0 * float(d_proj.max()) + 1e-3, (k, d_fold, d_proj)
+
+
+@pytest.mark.parametrize("name", ["track_kwin", "track_delta_kernel"])
+def test_tracker_window_bit_identical_knobs_at_full_size(dev, full_sd, knob, name):
+    """The two switches of the native window (csrc/api_trackwin.hip) whose branches exist only where dim % 128 == 0 (1408; the
+    mini geometry's 704 takes neither form), 1 against 0 on the bf16 engine over the 3 windows with 8 tracks of the test above.
+    The source states both bit-identical - track_kwin: the folded weights' products walk only the k-tiles of a tile's head, the
+    skipped tiles add zeros (l4p_gemm_desc.kw_cols); track_delta_kernel: i2t_delta_kernel (csrc/track.hip) forms the grouped GEMM's
+    sums in its order - so: torch.equal.
+    Measured (MI355X): both bit-identical in all three outputs."""
+    batch = make_batch(24, 8)
+    m = build_model(os.path.join(ROOT, "configs", "model.yaml"), precision="bf16")
+    m.load_state_dict({"l4p_model." + k: v for k, v in full_sd.items()})
+    out = []
+    with torch.no_grad():
+        for v in (1, 0):
+            knob(name, v)
+            out.append(m.forward({k: t.clone() for k, t in batch.items()}, ["track_2d"]))
+    torch.cuda.synchronize()
+    a, b = out
+    for k in ("track_2d_traj_est_bn2t", "track_2d_vis_est_bn1t", "track_2d_depth_est_bn1t"):
+        err = float((a[k].float() - b[k].float()).abs().max() / b[k].float().abs().max())
+        print(name, k, f"1 against 0: max {err:.2e} of the maximum")
+        assert torch.equal(a[k], b[k]), (name, k, err)
+

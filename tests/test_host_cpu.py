@@ -42,7 +42,7 @@ def test_abi_header_symbols_are_bound_and_exported():
     lib = _lib.load()  # resolves every symbol; raises if the .so lacks one
     for name in declared:
         assert hasattr(lib, name)
-    assert lib.l4p_abi_version() >= 1
+    assert lib.l4p_abi_version() == _lib.ABI_VERSION
     assert lib.l4p_prof_num_classes() >= 3
 
 
@@ -156,6 +156,36 @@ def test_library_load_brings_torch_runtime_first():
             "assert 'torch' in sys.modules; print('ok')") % ROOT
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and "ok" in out.stdout, out.stderr[-2000:]
+
+
+def test_launcher_knobs_start_from_their_environment_variables():
+    """Every launcher switch is a row of the knob table (csrc/prof.hip): the variable a process is started with is the knob's
+    value, its absence leaves the default, and no getenv is left outside the table.  One tracker knob, one GEMM launcher knob, in
+    fresh interpreters (the table is read once per process)."""
+    import subprocess
+    import sys
+
+    code = ("import sys; sys.path.insert(0, %r); from l4p_amd import _lib; lib = _lib.load(); "
+            "print(lib.l4p_get_knob(b'track_fold_i2t'), lib.l4p_get_knob(b'skinny_max_m'), lib.l4p_get_knob(b'gemm_t192'))") % ROOT
+    base = {k: v for k, v in os.environ.items() if k not in ("L4P_TRACK_FOLD_I2T", "L4P_SKINNY_MAX_M", "L4P_GEMM_T192")}
+    for env, want in (({}, "1 128 1"), ({"L4P_TRACK_FOLD_I2T": "0", "L4P_SKINNY_MAX_M": "64", "L4P_GEMM_T192": "0"}, "0 64 0")):
+        out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env={**base, **env})
+        assert out.returncode == 0 and out.stdout.split("\n")[-2] == want, (env, out.stdout, out.stderr[-2000:])
+    csrc = os.path.join(ROOT, "l4p_amd", "csrc")
+    sites = [f for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".hpp", ".inc")) and "getenv" in open(os.path.join(csrc, f)).read()]
+    assert sites == ["prof.hip"], sites
+
+
+def test_set_knob_bumps_the_knob_epoch():
+    """_lib.set_knob bumps _lib.knob_epoch when the library took the value, and only then (what Engine.track_window compares
+    before it trusts its cached workspace sizes: tests/test_track_gpu.py::test_tracker_window_knobs_one_against_zero)."""
+    lib = _lib.load()
+    before, value = _lib.knob_epoch, lib.l4p_get_knob(b"track_kwin")
+    _lib.set_knob("track_kwin", value)
+    assert _lib.knob_epoch == before + 1 and lib.l4p_get_knob(b"track_kwin") == value
+    with pytest.raises(_lib.L4PHipError):
+        _lib.set_knob("no_such_knob", 1)
+    assert _lib.knob_epoch == before + 1
 
 
 def test_isa_lint_parses_the_affected_instruction_form():

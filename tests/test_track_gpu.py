@@ -211,20 +211,16 @@ def test_single_window_entry_vs_reference_golden(dev, mini, precision):
 
 
 @pytest.mark.parametrize("precision", ["32-true", "bf16", "16-mixed"])
-@pytest.mark.parametrize("python_path", [False, True])
+@pytest.mark.parametrize("python_path", [False])  # (the True half ran the Python window, which is gone; the native cases keep their ids)
 def test_later_window_shared_half_equals_per_track_path(dev, mini, precision, python_path, monkeypatch):
     """Later windows: the second temporal half of every track's keys is encoder feature + the same mask
     token, so layer 0's t2i.k / t2i.v / i2t.q rows of that half are computed for track 0 and copied (hist_uniform = 2).
     Against every track projecting all of its rows (L4P_TRACK_HALF_SHARE=0): identical rows in, identical rows out - bit for
-    bit over a 4-window recursion, through the native window call and through the Python composition."""
+    bit over a 4-window recursion."""
     cfg, sd = mini
     model = build(cfg, sd, precision)
     batch = make_batch(40, 9)
     keys = ["track_2d_traj_est_bn2t", "track_2d_vis_est_bn1t", "track_2d_depth_est_bn1t"]
-    if python_path:
-        monkeypatch.setenv("L4P_TRACK_PYTHON", "1")
-    else:
-        monkeypatch.delenv("L4P_TRACK_PYTHON", raising=False)
     with torch.no_grad():
         monkeypatch.delenv("L4P_TRACK_HALF_SHARE", raising=False)
         a = model.forward({k: v.clone() for k, v in batch.items()}, ["track_2d"])
@@ -233,26 +229,6 @@ def test_later_window_shared_half_equals_per_track_path(dev, mini, precision, py
     torch.cuda.synchronize()
     for k in keys:
         assert a[k].shape[-1] == 40 and torch.equal(a[k], b[k]), (k, float((a[k] - b[k]).abs().max()))
-
-
-@pytest.mark.parametrize("precision", ["32-true", "bf16", "16-mixed"])
-def test_native_window_call_equals_python_composition(dev, mini, precision, monkeypatch):
-    """l4p_track_window_forward (one C++ call per clip and window, csrc/api_trackwin.hip) issues the same kernels in the same
-    order as sparse_heads._window (kernel by kernel from Python, L4P_TRACK_PYTHON=1): bit-identical outputs over a 3-window
-    recursion (shared first-window keys, per-track keys + memory tokens afterwards) and for 2 clips on their own streams."""
-    cfg, sd = mini
-    model = build(cfg, sd, precision)
-    b1 = make_batch(32, 7)
-    batch = {k: (torch.cat([v, v.flip(-1) if k == "rgb_b3thw" else v], dim=0) if torch.is_tensor(v) else v) for k, v in b1.items()}
-    keys = ["track_2d_traj_est_bn2t", "track_2d_vis_est_bn1t", "track_2d_depth_est_bn1t"]
-    with torch.no_grad():
-        monkeypatch.delenv("L4P_TRACK_PYTHON", raising=False)
-        a = model.forward({k: v.clone() for k, v in batch.items()}, ["track_2d"])
-        monkeypatch.setenv("L4P_TRACK_PYTHON", "1")
-        b = model.forward({k: v.clone() for k, v in batch.items()}, ["track_2d"])
-    torch.cuda.synchronize()
-    for k in keys:
-        assert a[k].shape[0] == 2 and torch.equal(a[k], b[k]), k
 
 
 def test_tracker_streams_beside_dense_heads_equal_serial(dev, mini, monkeypatch):
@@ -766,39 +742,32 @@ def _ctx_forms_equal(lib, dt, td, N, P, Cc, heads, tokens, knob):
         assert torch.equal(outs[0], outs[1]) and float(outs[0].float().abs().max()) > 0
 
 
-def test_folded_i2t_equals_projected_form(dev, mini, monkeypatch):
+def test_folded_i2t_equals_projected_form(dev, mini, knob):
     """The tracker with the image-side projections of its cross attentions folded into the token side (default: i2t.q / i2t.out of
     the image -> token attention, t2i.k / final.k of the token -> image attentions) against the form that projects every image
-    token (L4P_TRACK_FOLD_I2T=0 L4P_TRACK_FOLD_T2I=0): the same function of the same weights with the products associated
+    token (knobs track_fold_i2t = 0, track_fold_t2i = 0): the same function of the same weights with the products associated
     differently.  f32 engine: equal to rounding over a 4-window recursion with 9 tracks (1e-4 of the maximum),
     integer-valued outputs identical.  bf16 engine: two evaluation orders in bf16 are as far from each other as each is from the
     f32 result, so the folded form is held to the PROJECTED form's own per-track distance from the f32 engine: the median track must
     not be further from f32 than 1.5x the projected form's, and at most one of the nine tracks may have taken another branch (the
     recursion re-seeds queries at an argmax; measured: track 4 does, every other track sits at 3e-4 / 6e-3 in both forms).
-    Switched in the Python composition (the native call reads the switch once per process); the native window must equal the
-    Python composition bit for bit in the default form."""
+    Both forms run through the native window call (csrc/api_trackwin.hip), switched by its knobs."""
     cfg, sd = mini
     batch = make_batch(40, 9)
     keys = ["track_2d_traj_est_bn2t", "track_2d_vis_est_bn1t", "track_2d_depth_est_bn1t"]
     res = {}
     for precision in ("32-true", "bf16"):
         model = build(cfg, sd, precision)
-        monkeypatch.setenv("L4P_TRACK_PYTHON", "1")
         with torch.no_grad():
-            monkeypatch.setenv("L4P_TRACK_FOLD_I2T", "1")
-            monkeypatch.setenv("L4P_TRACK_FOLD_T2I", "1")
+            knob("track_fold_i2t", 1)
+            knob("track_fold_t2i", 1)
             a = model.forward({k: v.clone() for k, v in batch.items()}, ["track_2d"])
-            monkeypatch.setenv("L4P_TRACK_FOLD_I2T", "0")
-            monkeypatch.setenv("L4P_TRACK_FOLD_T2I", "0")  # (also switches the value fold off: it rides on the folded scores)
+            knob("track_fold_i2t", 0)
+            knob("track_fold_t2i", 0)  # (also switches the value fold off: it rides on the folded scores)
             b = model.forward({k: v.clone() for k, v in batch.items()}, ["track_2d"])
-            monkeypatch.delenv("L4P_TRACK_PYTHON")
-            monkeypatch.setenv("L4P_TRACK_FOLD_I2T", "1")
-            monkeypatch.setenv("L4P_TRACK_FOLD_T2I", "1")
-            c = model.forward({k: v.clone() for k, v in batch.items()}, ["track_2d"])
         torch.cuda.synchronize()
         res[precision] = (a, b)
         for k in keys:
-            assert torch.equal(a[k], c[k]), (precision, k, "native", float((a[k] - c[k]).abs().max()))
             assert torch.equal(a[k] == -10.0, b[k] == -10.0) and torch.equal(a[k] == 0.0, b[k] == 0.0), (precision, k)
         del model
     def per_track(x, y):  # rel-L2 of every track of clip 0
@@ -815,3 +784,36 @@ def test_folded_i2t_equals_projected_form(dev, mini, monkeypatch):
         # the typical track is as close to f32 in either form; at most one track of the nine may have taken another branch
         assert float(d_fold.median()) <= 1.5 * float(d_proj.median()) + 1e-4, (k, d_fold, d_proj)
         assert int((d_fold > 5 * d_proj.max() + 1e-3).sum()) <= 1, (k, d_fold, d_proj)
+
+
+@pytest.mark.parametrize("name", ["track_fold_l0", "track_ln_chain"])
+def test_tracker_window_knobs_one_against_zero(dev, mini, knob, name):
+    """Switches of the native window (csrc/api_trackwin.hip) that no other whole-tracker test flips and that act at the mini geometry,
+    1 against 0, over the 4-window recursion with 9 tracks of test_folded_i2t_equals_projected_form on the f32 engine.
+    track_fold_l0 (a later window's layer 0 folded or projected) and track_ln_chain (layer 1 re-derives layer 0's float keys from the
+    stored update and statistics, or reads the float master) reassociate like the two fold tests: their f32-engine bound, 1e-4 of the
+    maximum, and identical -10 / 0 marker values.  (track_kwin and track_delta_kernel are gated on dim % 128 == 0 and do nothing at
+    dim 704: tests/test_full_model_gpu.py flips them at the full geometry.)  The flips also move _lib.knob_epoch: the engine must
+    have dropped the workspace sizes it cached for the other setting.
+    Measured (MI355X): track_fold_l0 traj 3.2e-7, vis 3.3e-7, depth 2.3e-6 of the maximum; track_ln_chain 0 (the chain re-derives
+    the float keys bit for bit)."""
+    from l4p_amd import _lib
+
+    cfg, sd = mini
+    model = build(cfg, sd, "32-true")
+    batch = make_batch(40, 9)
+    eng = model.l4p_model.task_heads["track_2d"]._rt.engine
+    out = []
+    with torch.no_grad():
+        for v in (1, 0):
+            knob(name, v)
+            assert eng._trk_epoch != _lib.knob_epoch  # (stale until the next window looks)
+            out.append(model.forward({k: t.clone() for k, t in batch.items()}, ["track_2d"]))
+            assert eng._trk_epoch == _lib.knob_epoch and eng._trk_need
+    torch.cuda.synchronize()
+    a, b = out
+    for k in ("track_2d_traj_est_bn2t", "track_2d_vis_est_bn1t", "track_2d_depth_est_bn1t"):
+        err = float((a[k] - b[k]).abs().max() / b[k].abs().max())
+        print(name, k, f"1 against 0: max {err:.2e} of the maximum")
+        assert err <= 1e-4, (name, k, err)
+        assert torch.equal(a[k] == -10.0, b[k] == -10.0) and torch.equal(a[k] == 0.0, b[k] == 0.0), (name, k)

@@ -1,11 +1,11 @@
-"""Per-track distance of the bf16 tracker from the f32 tracker, folded vs projected image -> token attention (Python composition)."""
+"""Per-track distance of the bf16 tracker from the f32 tracker, folded vs projected image -> token attention (knob track_fold_i2t of the native window)."""
 import os
 import sys
 
-os.environ["L4P_TRACK_PYTHON"] = "1"
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
+from l4p_amd import _lib
 from l4p_amd.weights import ModelCfg, seeded_state_dict
 from tests.golden_utils import make_batch
 from tests.test_encoder_dpt_gpu import build
@@ -18,7 +18,7 @@ out = {}
 for prec in ("32-true", "bf16"):
     model = build(cfg, sd, prec)
     for fold in ("1", "0"):
-        os.environ["L4P_TRACK_FOLD_I2T"] = fold
+        _lib.set_knob("track_fold_i2t", int(fold))
         with torch.no_grad():
             o = model.forward({k: v.clone() for k, v in batch.items()}, ["track_2d"])
         out[(prec, fold)] = {k: v.float().cpu() for k, v in o.items() if torch.is_tensor(v)}

@@ -1,15 +1,15 @@
 """Full geometry: per-track distance of the bf16 tracker from the f32 tracker with the value projection of the token -> image
-attention folded (L4P_TRACK_FOLD_T2I_V=1) vs projected (=0), Python composition (the switch is read per call), and the distance
+attention folded (knob track_fold_t2i_v = 1) vs projected (= 0) in the native window, and the distance
 between a batch-1 and a batch-2 evaluation of the same clip in each form (what tests/test_full_model_gpu.py gates).
 usage: foldv_precision.py [queries=16] [frames=16]"""
 import os
 import sys
 
-os.environ["L4P_TRACK_PYTHON"] = "1"
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 sys.path.insert(0, ROOT)
+from l4p_amd import _lib
 from l4p_amd.models.utils import build_model
 from l4p_amd.weights import ModelCfg, seeded_state_dict
 from tests.golden_utils import make_batch
@@ -25,7 +25,7 @@ for prec in ("32-true", "bf16"):
     m = build_model(os.path.join(ROOT, "configs", "model.yaml"), precision=prec)
     m.load_state_dict({"l4p_model." + k: v for k, v in sd.items()})
     for fold in (["0"] if prec == "32-true" else ["1", "0"]):
-        os.environ["L4P_TRACK_FOLD_T2I_V"] = fold
+        _lib.set_knob("track_fold_t2i_v", int(fold))
         with torch.no_grad():
             o1 = m.forward({k: v.clone() for k, v in batch.items()}, ["track_2d"])
             o2 = m.forward({k: v.clone() for k, v in both.items()}, ["track_2d"]) if prec == "bf16" else None

@@ -29,7 +29,7 @@ zeros in one 16-byte pose row for lanes 48..63 of one wave.
                 s_waitcnt and compared with the final register (flags: bit j = load j of K0 K1 K2 depth P1 P0 P2 was not final;
                 a = [early P0.x, final P0.x, early P1.y, final P1.y])
   environment knobs worth combining: PYTORCH_NO_CUDA_MEMORY_CACHING=1, AMD_SERIALIZE_KERNEL=3, GPU_MAX_HW_QUEUES=1|8,
-  HSA_XNACK=0|1, L4P_TRACK_PYTHON=1 (tracker kernel by kernel from Python instead of one native call per window)
+  HSA_XNACK=0|1
 """
 import argparse
 import ctypes as C
@@ -73,8 +73,8 @@ vlib.race_victim_cnt_launch.argtypes = [C.c_void_p] * 5 + [C.c_int] * 4 + [C.c_u
 
 dev = torch.device("cuda")
 print("device:", torch.cuda.get_device_properties(0).gcnArchName, "| env:",
-      {k: os.environ[k] for k in ("PYTORCH_NO_CUDA_MEMORY_CACHING", "AMD_SERIALIZE_KERNEL", "GPU_MAX_HW_QUEUES", "HSA_XNACK",
-                                  "L4P_TRACK_PYTHON") if k in os.environ}, "| args:", vars(args))
+      {k: os.environ[k] for k in ("PYTORCH_NO_CUDA_MEMORY_CACHING", "AMD_SERIALIZE_KERNEL", "GPU_MAX_HW_QUEUES", "HSA_XNACK")
+                                  if k in os.environ}, "| args:", vars(args))
 g = torch.Generator().manual_seed(3)
 H = W = 224
 F = 3
