@@ -1,10 +1,12 @@
 """The generic-video part of the reference's demo (demo/demo.py:80-112) on the MI355X engine: VideoDataset ->
-DataLoader(batch_size=1) -> prepare_model(...).forward(batch, tasks).  The 2D visualisations (l4p/utils/vis.py, viser) are out of
-scope; the outputs are reported (and optionally saved as .npz) instead.  --recon4d DIR adds the camray task and writes the 4D
-reconstruction of the reference's 4D sections (generate_4D_visualization, demo.py:116-258) as PLY files under DIR.
+DataLoader(batch_size=1) -> prepare_model(...).forward(batch, tasks).  The outputs are reported (and optionally saved as .npz).
+--vis DIR writes the reference's side-by-side result video (generate_video_visualizations, demo.py:78,113: RGB, depth, flow, motion
+mask, track trails) rendered on the GPU; --recon4d DIR adds the camray task and writes the 4D reconstruction of the reference's 4D
+sections (generate_4D_visualization, demo.py:116-258) as PLY files under DIR.  The viser viewer stays out of scope.
 
   python demo/demo.py --videos a.mp4 b.mp4 --ckpt weights/l4p_depth_flow_2d3dtrack_camray_dynseg_v1.ckpt   # needs mediapy
   python demo/demo.py --synthetic                      # no checkpoint / video files here: seeded weights + a seeded video
+  python demo/demo.py --synthetic --vis out/           # + the five-panel result video (.mp4 with mediapy, PNG frames without)
   python demo/demo.py --synthetic --recon4d out/       # + 4D point clouds / track trails / frusta as PLY under out/
 
 With --synthetic the weights are the name-seeded random tensors of the test-suite (same 916-key state dict a checkpoint
@@ -35,6 +37,9 @@ def main():
     ap.add_argument("--max-queries", type=int, default=128)
     ap.add_argument("--spacing", type=float, default=0.04, help="track_2d_querry_sampling_spacing (625 queries at 0.04)")
     ap.add_argument("--save", default=None, help="directory for <seq_name>.npz")
+    ap.add_argument("--vis", default=None, metavar="DIR",
+                    help="write each video's 2D result video (RGB | depth | flow | motion mask | tracks; "
+                         "l4p_amd.utils.vis2d.generate_video_visualizations) under DIR")
     ap.add_argument("--recon4d", default=None, metavar="DIR",
                     help="also run the camray task and write each video's 4D reconstruction (world point clouds, 3D track trails, "
                          "camera frusta as PLY; l4p_amd.utils.recon4d.generate_4D_visualization) under DIR")
@@ -82,8 +87,31 @@ def main():
             os.makedirs(args.save, exist_ok=True)
             np.savez_compressed(os.path.join(args.save, os.path.splitext(batch["seq_name"][0])[0] + ".npz"),
                                 **{k: v.float().cpu().numpy() for k, v in out.items() if torch.is_tensor(v)})
+        if args.vis:
+            vis_2d(batch, out, tasks, args.vis)
         if args.recon4d:
             recon_4d(batch, out, tasks, args.recon4d)
+
+
+def vis_2d(batch, out, tasks, out_dir):
+    """generate_video_visualizations split into its GPU part (render + the one copy to the host) and its file writing, each timed on
+    its own."""
+    from l4p_amd.utils import vis2d
+
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    res = vis2d.render_video_panels(batch, out, tasks)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    vid = res["video"].cpu().numpy()
+    t2 = time.perf_counter()
+    name = vis2d.write_video(vid, out_dir, batch["seq_name"][0])
+    t3 = time.perf_counter()
+    lo, hi = res["depth_range"].tolist()
+    panels = vid.shape[2] // batch["rgb_b3thw"].shape[-1]
+    print(f"  2D: {vid.shape[0]} frames of {panels} panels, depth range {lo:.3g} .. {hi:.3g}, flow radius "
+          f"{float(res['flow_rad_max'][0]):.3g}; GPU render {(t1 - t0) * 1e3:.1f} ms, copy to host {(t2 - t1) * 1e3:.1f} ms, file writing "
+          f"{(t3 - t2) * 1e3:.0f} ms -> {name}")
 
 
 def recon_4d(batch, out, tasks, out_dir):

@@ -43,7 +43,8 @@ typedef void* l4p_stream; /* hipStream_t */
 typedef struct l4p_engine l4p_engine;
 
 const char* l4p_last_error(void);
-int l4p_abi_version(void); /* 12: every launcher switch is a knob; 11: 4D reconstruction (l4p_recon_cameras, l4p_point_map,
+int l4p_abi_version(void); /* 13: the 2D result video (l4p_vis_stats, l4p_vis_panels, l4p_vis_track_prep, l4p_vis_track_raster);
+                              * 12: every launcher switch is a knob; 11: 4D reconstruction (l4p_recon_cameras, l4p_point_map,
                               * l4p_track_point_map, l4p_recon_track_prep, l4p_recon_track_scale, l4p_recon_trails);
                               * 10: l4p_gemm_desc.kw_cols / kw_len, l4p_t2i_context(shared_from); 9: l4p_similarity_prefix, knobs attn64 / probe_kernels; 8: l4p_gemm_desc.ups_hi / ups_wi; 7: L4P_F16; 6: l4p_set_knob / l4p_get_knob; 5: l4p_layernorm_res(out_stats), l4p_layernorm_chain, l4p_stream_create_cu_mask; 4: l4p_gemm_desc.o_gs, l4p_i2t_delta,
                               * l4p_t2i_probs, l4p_t2i_context; 3: l4p_gemm_desc.w_gr / w_gs / b_gs, l4p_i2t_probs,
@@ -404,6 +405,41 @@ int l4p_recon_track_scale(l4p_stream stream, const float* ratios, long long n, l
  * colours -> xyz [total][3], rgb [total][3], total = off[T].  total = 0 launches nothing. */
 int l4p_recon_trails(l4p_stream stream, const float* X, const int* slot, const long long* off, const unsigned char* lut, int N,
                      int T, int trail, int seg, long long total, float* xyz, unsigned char* rgb);
+
+/* ------------------------------------------------------------------------------------------------
+ * The 2D result video (generate_video_visualizations, l4p/utils/vis.py:34-104) of one clip (batch element 0): RGB, turbo depth,
+ * colour-wheel flow, thresholded motion mask and track trails over the grey video side by side, out [T][H][P W][3] float or
+ * uchar (the project's own byte rule min(255, max(0, x * 255 + 0.5)) truncated).  f32 where the reference computes in torch f32,
+ * f64 where it computes in Python floats / numpy float64 (the flow panel from its clip on, under NumPy 2 promotion).
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Statistics (vis.py:60-63, 413-417), one launch: depth [n] (or NULL), flow [2][n] (or NULL) -> stats [3] uint: [0] = ~bits of the
+ * smallest positive depth (0: none), [1] = bits of the largest, [2] = bits of max(u * u + v * v).  The consumers form
+ * depth_range = (max(min, 0.05), min(max, 20)) and rad_max = min(25, sqrt(.)) from them in double. */
+int l4p_vis_stats(l4p_stream stream, const float* depth, const float* flow, long long n, unsigned* stats);
+/* The fused dense panels (vis.py:48-50 rgb * std + mean; :57-67 with colormap_image :227-282, turbo [256][3] float already
+ * flipped; :69-77 with flow_video_to_color_with_bounds / flow_to_color_with_bounds / flow_uv_to_colors :338-428, wheel [55][3]
+ * double = make_colorwheel() / 255.0; :79-87 sigmoid > 0.85; the grey background of visualize_2d_tracks :453, :464-465).
+ * rgb [3][T][H][W], depth / mask [T][H][W], flow [2][T][H][W]; P panels per row, rgb in slot 0, p_* = the slot of each task or
+ * -1.  out_u8 != 0 with a track panel: the grey background goes to grey [T][H][W] float for l4p_vis_track_raster instead.
+ * scalars [3] double receives depth_range (NaN, NaN and an all-zero depth panel when no depth is positive) and rad_max. */
+int l4p_vis_panels(l4p_stream stream, const float* rgb, const float* mean, const float* stdv, const float* depth, const float* flow,
+                   const float* mask, const unsigned* stats, const float* turbo, const double* wheel, int T, int H, int W, int P,
+                   int p_depth, int p_flow, int p_mask, int p_track, void* out, int out_u8, float* grey, double* scalars);
+/* Display list of the track panel (visualize_2d_tracks vis.py:454-466, plot_2d_tracks :479-483, :500-502, :514-515): order [N] =
+ * stable argsort of key_traj[:, 1, 0] (the batch's trajectory; ties to the lower index); per frame t and rank i: xy [T][N][2] =
+ * the estimate traj [N][2][T] of track order[i] rounded half to even, vis [T][N] = sigmoid(vis_logit [N][T]) > vis_thr (and the
+ * coordinates finite), colors [N][3] float = hsv [256][3] double at Normalize(0, N - 1)(i). */
+int l4p_vis_track_prep(l4p_stream stream, const float* key_traj, const float* traj, const float* vis_logit, const double* hsv,
+                       int N, int T, float vis_thr, int* order, int* xy, unsigned char* vis, float* colors);
+/* Track raster (plot_2d_tracks vis.py:489-521; cv2.line LINE_AA / cv2.addWeighted / cv2.circle replaced by the project's own
+ * rules): per frame the trail steps s of the last `trail` frames in order, each: segments in ascending rank with
+ * coverage clamp(1 - distance, 0, 1), then the blend alpha F + (1 - alpha) G with the step's start G, alpha = (s + 1) / (L - 1);
+ * then the discs dx^2 + dy^2 <= 5 in ascending rank.  src: background, pixel (t, y, x) at t * s_frame + y * s_row + x * s_px (may
+ * alias out); out pixel (t, y, x) channel c at t * o_frame + y * o_row + x * 3 + c, float or uchar (out_u8).  N = 0 copies. */
+int l4p_vis_track_raster(l4p_stream stream, const int* xy, const unsigned char* vis, const float* colors, int N, int T, int H,
+                         int W, int trail, const float* src, long long s_px, long long s_row, long long s_frame, void* out,
+                         long long o_row, long long o_frame, int out_u8);
 
 /* ------------------------------------------------------------------------------------------------
  * SAM-style point tracker (sparse_heads.py, sam/{prompt_encoder,transformer,mask_decoder}.py).

@@ -8,6 +8,7 @@
 #include "common.hpp"
 #include "prof.hpp"
 #include "unproject.hpp"
+#include "stable_argsort.hpp"  // recon_argsort_kernel: the height order of the tracks (vis.py:722), shared with vis2d.hip
 
 // 4x4 inverse in double, Gauss-Jordan with partial pivoting (row-major in and out)
 __device__ void inv4_d(const double* a, double* o) {
@@ -154,27 +155,6 @@ __global__ void recon_track_points_kernel(const float* __restrict__ traj, const 
     const float X = (x - k[2 * T]) * Z / k[0], Y = (y - k[6 * T]) * Z / k[5 * T];
     float* o = out + bi * 3 * T + t;
     for (int c = 0; c < 3; ++c) o[(long long)c * T] = p[(c * 4 + 0) * T] * X + p[(c * 4 + 1) * T] * Y + p[(c * 4 + 2) * T] * Z + p[(c * 4 + 3) * T];
-}
-
-// -------------------------------------------------------------------------------------------------
-// Stable argsort of the N initial y values (torch.argsort(traj[:, :, 1, 0], stable=True); vis.py:722): the rank of element
-// n is the number of elements that sort before it, ties to the lower index, NaN last.  O(N^2) comparisons spread over N waves
-// (the query counts of the demo: 625).
-// -------------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool sorts_before(float a, int ia, float b, int ib) {
-    const bool na = a != a, nb = b != b;
-    if (na || nb) return (!na && nb) || (na && nb && ia < ib);
-    return a < b || (a == b && ia < ib);
-}
-// one wave per element: the lanes count over strided slices of the N keys (L2-resident), then a butterfly sum
-__global__ __launch_bounds__(256) void recon_argsort_kernel(const float* __restrict__ traj, int N, int T, int* __restrict__ order) {
-    const int n = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
-    if (n >= N) return;  // (wave-uniform)
-    const float y = traj[((long long)n * 2 + 1) * T];
-    int rank = 0;
-    for (int j = lane; j < N; j += 64) rank += sorts_before(traj[((long long)j * 2 + 1) * T], j, y, n) ? 1 : 0;
-    for (int o = 32; o > 0; o >>= 1) rank += __shfl_xor(rank, o);
-    if (lane == 0) order[rank] = n;
 }
 
 // -------------------------------------------------------------------------------------------------
