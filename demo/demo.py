@@ -1,4 +1,5 @@
-"""The generic-video part of the reference's demo (demo/demo.py:80-112) on the MI355X engine: VideoDataset ->
+"""The reference's demo (demo/demo.py:45-258) on the MI355X engine: VideoDataset (--videos, its sections 2 / 4), DavisDataset (--davis,
+sections 1 / 3) or DycheckDataset (--dycheck, section 5: the camera file's intrinsics, use_intrinsics=True) ->
 DataLoader(batch_size=1) -> prepare_model(...).forward(batch, tasks).  The outputs are reported (and optionally saved as .npz).
 --vis DIR writes the reference's side-by-side result video (generate_video_visualizations, demo.py:78,113: RGB, depth, flow, motion
 mask, track trails) rendered on the GPU; --recon4d DIR adds the camray task and writes the 4D reconstruction of the reference's 4D
@@ -8,13 +9,18 @@ sections (generate_4D_visualization, demo.py:116-258) as PLY files under DIR.  T
   python demo/demo.py --synthetic                      # no checkpoint / video files here: seeded weights + a seeded video
   python demo/demo.py --synthetic --vis out/           # + the five-panel result video (.mp4 with mediapy, PNG frames without)
   python demo/demo.py --synthetic --recon4d out/       # + 4D point clouds / track trails / frusta as PLY under out/
+  python demo/demo.py --davis DAVIS_ROOT --ckpt ...    # JPEGImages/480p/<seq>, Annotations/480p/<seq>: queries on the instance masks
+  python demo/demo.py --dycheck DYCHECK_ROOT --ckpt ... --recon4d out/   # <seq>/dense/images, <seq>/calibration.txt
+  python demo/demo.py --synthetic --davis X --vis out/ # a small seeded DAVIS (or --dycheck: DyCheck) tree in a temporary directory
 
 With --synthetic the weights are the name-seeded random tensors of the test-suite (same 916-key state dict a checkpoint
 holds) and the "video" is l4p_amd.data.synthetic.synthetic_video: the point is the plumbing and the timing, not the pictures.
 """
 import argparse
+import contextlib
 import os
 import sys
+import tempfile
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,19 +29,26 @@ sys.path.insert(0, ROOT)
 import numpy as np
 import torch
 
-from l4p_amd.data import VideoDataset
+from l4p_amd.data import DavisDataset, DycheckDataset, VideoDataset
 from l4p_amd.models.utils import build_model, prepare_model
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--videos", nargs="*", default=[])
+    ap.add_argument("--davis", default=None, metavar="ROOT",
+                    help="a DAVIS tree (the reference demo's sections 1 / 3): queries sampled on the instance masks at spacing 0.02; "
+                         "with --recon4d the crop is (56, 224, 224).  With --synthetic: a seeded tree in a temporary directory")
+    ap.add_argument("--dycheck", default=None, metavar="ROOT",
+                    help="a DyCheck tree (section 5): resize (298, 224), stride 2, spacing 0.04, camray with the camera file's "
+                         "intrinsics (use_intrinsics=True).  With --synthetic: a seeded tree in a temporary directory")
     ap.add_argument("--ckpt", default=None)
     ap.add_argument("--config", default=os.path.join(ROOT, "configs", "model.yaml"))
     ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--frames", type=int, default=64, help="crop_size[0] (the demo uses 64, or 16 to limit memory)")
     ap.add_argument("--max-queries", type=int, default=128)
-    ap.add_argument("--spacing", type=float, default=0.04, help="track_2d_querry_sampling_spacing (625 queries at 0.04)")
+    ap.add_argument("--spacing", type=float, default=None,
+                    help="track_2d_querry_sampling_spacing (default 0.04 = 625 queries; 0.02 for --davis, as the reference demo)")
     ap.add_argument("--save", default=None, help="directory for <seq_name>.npz")
     ap.add_argument("--vis", default=None, metavar="DIR",
                     help="write each video's 2D result video (RGB | depth | flow | motion mask | tracks; "
@@ -45,12 +58,44 @@ def main():
                          "camera frusta as PLY; l4p_amd.utils.recon4d.generate_4D_visualization) under DIR")
     ap.add_argument("--precision", default="16-mixed",
                     help="engine: 16-mixed (the reference demo's own, IEEE half; default) | bf16 (what bench.py measures) | 32-true")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
+    if sum(bool(v) for v in (args.videos, args.davis, args.dycheck)) > 1:
+        ap.error("--videos, --davis and --dycheck are one input each: give one")
+    if not args.synthetic and not (args.ckpt and (args.videos or args.davis or args.dycheck)):
+        ap.error("--ckpt and one of --videos / --davis / --dycheck (or --synthetic)")
+    if args.spacing is None:
+        args.spacing = 0.02 if args.davis else 0.04  # demo.py:50,133 / :88,221
+    return args
 
-    precision, accelerator = args.precision, "gpu"  # demo.py:22-23 hard-codes "16-mixed"
+
+def plan(args):
+    """(tasks, dataset keyword arguments) of the reference demo's section that ``args`` selects."""
     tasks = ["depth", "flow_2d_backward", "dyn_mask", "track_2d"]  # demo.py:82,99
-    if args.recon4d:
+    if args.recon4d or args.dycheck:
         tasks.append("camray")  # the reference's 4D sections (demo.py:116-258) add it
+    kw = dict(crop_size=(args.frames, 224, 224), estimation_directions=[1], track_2d_querry_sampling_spacing=args.spacing)
+    if args.davis and args.recon4d:
+        kw["crop_size"] = (56, 224, 224)  # demo.py:131
+    if args.dycheck:
+        kw.update(resize_size=(298, 224), stride=2)  # demo.py:216-224
+    return tasks, kw
+
+
+def synthetic_tree(args, tmp):
+    """--synthetic --davis / --dycheck: a small seeded tree (PNG-encoded frames, palette masks, a calibration.txt) under ``tmp``."""
+    from l4p_amd.data.synthetic import synthetic_masks, synthetic_video, write_davis_tree, write_dycheck_tree
+
+    if args.davis:
+        frames = synthetic_video(1, 20, 120, 214)
+        return write_davis_tree(os.path.join(tmp, "davis"), "synthetic", frames, synthetic_masks(2, 20, 120, 214, "blob"), "P")
+    frames = synthetic_video(1, 24, 181, 135)
+    return write_dycheck_tree(os.path.join(tmp, "dycheck"), "synthetic", frames, (403.217, 398.06, 66.9, 91.325))
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    precision, accelerator = args.precision, "gpu"  # demo.py:22-23 hard-codes "16-mixed"
+    tasks, kw = plan(args)
     frames = None
     if args.synthetic:
         from l4p_amd.weights import ModelCfg, seeded_state_dict
@@ -59,16 +104,37 @@ def main():
         model = build_model(args.config, max_queries=args.max_queries, precision=precision)
         model.load_state_dict({"l4p_model." + k: v for k, v in seeded_state_dict(ModelCfg.full()).items()})
         model = model.eval()
-        args.videos = ["synthetic/480p.mp4"]
-        frames = {args.videos[0]: synthetic_video(1, 50, 480, 854)}
+        if not (args.davis or args.dycheck):
+            args.videos = ["synthetic/480p.mp4"]
+            frames = {args.videos[0]: synthetic_video(1, 50, 480, 854)}
     else:
-        assert args.ckpt and args.videos, "--ckpt and --videos (or --synthetic)"
         model = prepare_model(model_config_path=args.config, ckpt_path=args.ckpt, max_queries=args.max_queries,
                               precision=precision, accelerator=accelerator)
 
     model.l4p_model.window_batch = 8  # windows of a long clip go through encoder + dense decoders eight at a time
-    dataset = VideoDataset(video_paths=args.videos, crop_size=(args.frames, 224, 224), estimation_directions=[1],
-                           track_2d_querry_sampling_spacing=args.spacing, frames=frames)
+    with contextlib.ExitStack() as stack:
+        if args.synthetic and (args.davis or args.dycheck):
+            root = synthetic_tree(args, stack.enter_context(tempfile.TemporaryDirectory()))
+        else:
+            root = args.davis or args.dycheck
+        if args.davis:
+            dataset = DavisDataset(data_root=root, **kw)
+        elif args.dycheck:
+            dataset = DycheckDataset(data_root=root, **kw)
+        else:
+            dataset = VideoDataset(video_paths=args.videos, frames=frames, **kw)
+        camray = model.l4p_model.task_heads["camray"] if "camray" in tasks else None
+        saved = camray.use_intrinsics if camray is not None else None
+        if args.dycheck:
+            camray.use_intrinsics = True  # demo.py:226: pose from the rays and the INPUT intrinsics
+        try:
+            run(args, model, dataset, tasks)
+        finally:
+            if args.dycheck:
+                camray.use_intrinsics = saved  # demo.py:258
+
+
+def run(args, model, dataset, tasks):
     loader = torch.utils.data.DataLoader(dataset, batch_size=1, shuffle=False)
     for batch in loader:
         torch.cuda.synchronize()

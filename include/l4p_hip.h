@@ -43,7 +43,8 @@ typedef void* l4p_stream; /* hipStream_t */
 typedef struct l4p_engine l4p_engine;
 
 const char* l4p_last_error(void);
-int l4p_abi_version(void); /* 13: the 2D result video (l4p_vis_stats, l4p_vis_panels, l4p_vis_track_prep, l4p_vis_track_raster);
+int l4p_abi_version(void); /* 14: DAVIS / DyCheck datasets (l4p_pil_nearest_table, l4p_torch_nearest_table, l4p_instance_mask_clip,
+                              * l4p_seg_query_select); 13: the 2D result video (l4p_vis_stats, l4p_vis_panels, l4p_vis_track_prep, l4p_vis_track_raster);
                               * 12: every launcher switch is a knob; 11: 4D reconstruction (l4p_recon_cameras, l4p_point_map,
                               * l4p_track_point_map, l4p_recon_track_prep, l4p_recon_track_scale, l4p_recon_trails);
                               * 10: l4p_gemm_desc.kw_cols / kw_len, l4p_t2i_context(shared_from); 9: l4p_similarity_prefix, knobs attn64 / probe_kernels; 8: l4p_gemm_desc.ups_hi / ups_wi; 7: L4P_F16; 6: l4p_set_knob / l4p_get_knob; 5: l4p_layernorm_res(out_stats), l4p_layernorm_chain, l4p_stream_create_cu_mask; 4: l4p_gemm_desc.o_gs, l4p_i2t_delta,
@@ -695,6 +696,39 @@ int l4p_clip_resize_normalize(l4p_stream stream, const unsigned char* frames, co
  * kernel evaluates them (float32, source coordinate = one fma): output j (0 <= j < out_size) of the crop starting at
  * crop0 of the axis resized in_size -> res_size reads i0[j], i1[j] with weights 1 - lambda1[j], lambda1[j]. */
 int l4p_resize_index_table(int in_size, int res_size, int crop0, int out_size, int* i0, int* i1, float* lambda1);
+
+/* ------------------------------------------------------------------------------------------------
+ * DAVIS / DyCheck datasets: the per-pixel work the instance masks add (l4p/data/davis.py:96-110) and the query
+ * selection of sample_tracks, version "uniform_over_seg" (l4p/data/l4p_dataset_mini.py:450-465).
+ * ------------------------------------------------------------------------------------------------ */
+
+/* HOST function: the source index of every output position of PIL.Image.resize(..., NEAREST) along one full axis
+ * (what Image.resize does to mode "P" / "1" images whatever filter is asked for: davis.py:101-102 on a palette
+ * annotation).  _imaging.c _resize + libImaging/Geometry.c ImagingScaleAffine: the source coordinate starts at
+ * half a step and is accumulated in double.  idx: host int[out_size]. */
+int l4p_pil_nearest_table(int in_size, int out_size, int* idx);
+
+/* HOST function: the source index of F.interpolate(mode="nearest") given `size` along one axis
+ * (l4p_dataset_mini.py:266 for instanceseg_b1thw; ATen nearest_idx, float32 scale).  idx: host int[out_size]. */
+int l4p_torch_nearest_table(int in_size, int out_size, int* idx);
+
+/* mask_out[t][y][x] (float, [T_out][out_h][out_w] = instanceseg_b1thw) =
+ *   float(src[frame_index[t]][ytab[y]][xtab[x]] > 0)
+ * src: uint8 annotation frames [n_src][in_h][in_w] with pix_stride bytes between pixels (3 reads the first channel
+ * of an RGB annotation in place).  Replaces davis.py:98-110 (Pillow round trip of a palette mask, to_tensor[:1],
+ * mean over the size-1 dimension > 0), the mirror padding, F.interpolate(nearest) (l4p_dataset_mini.py:266) and the
+ * centre crop (:315-337): frame_index (device int[T_out]) is the table of l4p_clip_resize_normalize; ytab / xtab
+ * (device int[out_h] / int[out_w]) are the index maps of those stages composed on the host.  An entry outside the
+ * source gives NaN. */
+int l4p_instance_mask_clip(l4p_stream stream, const unsigned char* src, int n_src, int in_h, int in_w, int pix_stride,
+                           const int* frame_index, const int* ytab, const int* xtab, float* mask_out, int T_out,
+                           int out_h, int out_w);
+
+/* Query selection of sample_tracks "uniform_over_seg" (l4p_dataset_mini.py:450-465): candidate m with cell
+ * (cells[2m], cells[2m+1]) = (x_id, y_id) is kept iff the 3x3 erosion of mask [h][w] (float; neighbours outside
+ * the image ignored, kornia's default border) is > 0 there.  sel (device int[M]) receives the kept m in ascending
+ * order, *count (device int) their number; when none is kept, sel = 0..M-1 and *count = M (:462-463). */
+int l4p_seg_query_select(l4p_stream stream, const float* mask, int h, int w, const int* cells, int M, int* sel, int* count);
 
 #ifdef __cplusplus
 }

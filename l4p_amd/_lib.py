@@ -14,7 +14,7 @@ L4P_BF16 = 0
 L4P_F32 = 1
 L4P_F16 = 2  # IEEE half storage / f16 MFMA: the arithmetic class of the reference's "16-mixed" (fp16 autocast)
 
-ABI_VERSION = 13  # what l4p_abi_version() of the library this binding was written against returns (include/l4p_hip.h)
+ABI_VERSION = 14  # what l4p_abi_version() of the library this binding was written against returns (include/l4p_hip.h)
 
 EPI_DENSE, EPI_QKV, EPI_CONVT, EPI_MASKDOT = 0, 1, 2, 3
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
@@ -154,6 +154,10 @@ SIGNATURES = {
     "l4p_pil_resample_u8": (_I, [_VP, _VP, _VP, _LL, _I, _I, _I, _I, _I, _VP, _VP, _I]),
     "l4p_clip_resize_normalize": (_I, [_VP, _VP, _VP, _VP] + [_I] * 9 + [_VP, _VP, _I, _VP, _VP, _I, _VP]),
     "l4p_resize_index_table": (_I, [_I, _I, _I, _I, _VP, _VP, _VP]),
+    "l4p_pil_nearest_table": (_I, [_I, _I, _VP]),
+    "l4p_torch_nearest_table": (_I, [_I, _I, _VP]),
+    "l4p_instance_mask_clip": (_I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _I, _I, _I]),
+    "l4p_seg_query_select": (_I, [_VP, _VP, _I, _I, _VP, _I, _VP, _VP]),
     "l4p_track_readout": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I]),
     "l4p_track_prepare": (_I, [_VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _I]),
     "l4p_track_commit": (_I, [_VP] * 9 + [_I] * 5 + [_VP] * 5 + [_I, _I]),

@@ -282,6 +282,68 @@ __global__ __launch_bounds__(256) void clip_resize_normalize_kernel(ClipArgs a) 
     }
 }
 
+// ---- DAVIS instance masks and query selection (l4p/data/davis.py:96-110, l4p_dataset_mini.py:450-465) ----------------------------
+
+// out[t][y][x] = float(src[frame_index[t]][ytab[y]][xtab[x]] > 0).  Every stage of the reference between the decoded annotation and
+// the prepared mask is an index map (Pillow NEAREST down and up for palette masks, torch nearest, the crop) or, for grey-scale
+// annotations, comes after the bilinear round trip that the resample passes above have already run: the host composes the maps into
+// ytab / xtab and a frame costs out_h * out_w byte reads.  A table entry outside the source writes NaN (never an out-of-range read).
+__global__ __launch_bounds__(256) void instance_mask_clip_kernel(const uint8_t* __restrict__ src, int n_src, int in_h, int in_w,
+                                                                 int pix_stride, const int* __restrict__ frame_index,
+                                                                 const int* __restrict__ ytab, const int* __restrict__ xtab,
+                                                                 float* __restrict__ out, int T_out, int out_h, int out_w) {
+    const int per_frame = out_h * out_w;
+    const long long total = (long long)T_out * per_frame;
+    for (long long i = blockIdx.x * 256ll + threadIdx.x; i < total; i += gridDim.x * 256ll) {
+        const int t = (int)(i / per_frame);
+        const int r = (int)(i - (long long)t * per_frame);
+        const int oy = r / out_w, ox = r - oy * out_w;
+        const int f = frame_index[t], y = ytab[oy], x = xtab[ox];
+        float v = __builtin_nanf("");
+        if ((unsigned)f < (unsigned)n_src && (unsigned)y < (unsigned)in_h && (unsigned)x < (unsigned)in_w)
+            v = src[(((long long)f * in_h + y) * in_w + x) * pix_stride] > 0 ? 1.f : 0.f;
+        out[i] = v;
+    }
+}
+
+// One workgroup (4 waves).  Candidate m is kept iff the 3x3 erosion of the mask (out-of-image neighbours ignored: kornia's default
+// "geodesic" border) is > 0 at its cell; kept candidates are written in ascending m (ballot + popcount inside a wave, the four wave
+// totals through LDS, chunks of 256 candidates in order).  Nothing kept: sel = identity, count = M (l4p_dataset_mini.py:462-463).
+__global__ __launch_bounds__(256) void seg_query_select_kernel(const float* __restrict__ mask, int h, int w,
+                                                               const int* __restrict__ cells, int M, int* __restrict__ sel,
+                                                               int* __restrict__ count) {
+    __shared__ int wave_total[4];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int base = 0;
+    for (int m0 = 0; m0 < M; m0 += 256) {
+        const int m = m0 + threadIdx.x;
+        bool keep = false;
+        if (m < M) {
+            const int cx = cells[2 * m], cy = cells[2 * m + 1];
+            keep = cx >= 0 && cx < w && cy >= 0 && cy < h;
+            if (keep) {
+                for (int dy = -1; dy <= 1; ++dy)
+                    for (int dx = -1; dx <= 1; ++dx) {
+                        const int y = cy + dy, x = cx + dx;
+                        if (y >= 0 && y < h && x >= 0 && x < w) keep = keep && mask[(long long)y * w + x] > 0.f;
+                    }
+            }
+        }
+        const unsigned long long b = __ballot(keep);
+        const int before = __popcll(b & ((1ull << lane) - 1ull));
+        if (lane == 0) wave_total[wave] = __popcll(b);
+        __syncthreads();
+        int off = base;
+        for (int k = 0; k < wave; ++k) off += wave_total[k];
+        if (keep) sel[off + before] = m;
+        base += wave_total[0] + wave_total[1] + wave_total[2] + wave_total[3];
+        __syncthreads();
+    }
+    if (base == 0)
+        for (int m = threadIdx.x; m < M; m += 256) sel[m] = m;
+    if (threadIdx.x == 0) *count = base == 0 ? M : base;
+}
+
 int grid_for(long long threads) {
     const long long b = (threads + 255) / 256;
     return (int)(b < 1 ? 1 : (b > 8192 ? 8192 : b));
@@ -446,6 +508,76 @@ int l4p_clip_resize_normalize(l4p_stream s, const unsigned char* frames, const i
         hipLaunchKernelGGL(clip_resize_normalize_kernel<true>, dim3(grid), dim3(256), 0, stream, a);
     else
         hipLaunchKernelGGL(clip_resize_normalize_kernel<false>, dim3(grid), dim3(256), 0, stream, a);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int l4p_pil_nearest_table(int in_size, int out_size, int* idx) {
+    if (in_size <= 0 || out_size <= 0 || !idx) {
+        l4p_set_error("pil_nearest_table: bad arguments");
+        return L4P_E_INVALID;
+    }
+    // _imaging.c _resize (NEAREST: an affine transform with a[0] = size ratio) -> Geometry.c ImagingScaleAffine: the source
+    // coordinate starts at half a step and is ACCUMULATED in double, one addition per output position; COORD truncates
+    const double a0 = (double)((float)in_size - 0.f) / out_size;  // (the box is a float[4])
+    double xo = 0.0 + a0 * 0.5;
+    for (int x = 0; x < out_size; ++x) {
+        int xin = xo < 0.0 ? -1 : (int)xo;
+        if (xin < 0 || xin >= in_size) {  // Pillow leaves such a pixel at its fill value; not reachable for a full-axis box
+            l4p_set_error("pil_nearest_table: source index %d outside [0,%d)", xin, in_size);
+            return L4P_E_INVALID;
+        }
+        idx[x] = xin;
+        xo += a0;
+    }
+    return 0;
+}
+
+int l4p_torch_nearest_table(int in_size, int out_size, int* idx) {
+    if (in_size <= 0 || out_size <= 0 || !idx) {
+        l4p_set_error("torch_nearest_table: bad arguments");
+        return L4P_E_INVALID;
+    }
+    // ATen UpSampleKernel.cpp nearest_idx: identity and the exact doubling are special-cased, otherwise
+    // min(floorf(dst * scale), in - 1) with scale = (float)in / out
+    const float scale = (float)in_size / (float)out_size;
+    for (int x = 0; x < out_size; ++x) {
+        int v;
+        if (out_size == in_size)
+            v = x;
+        else if (out_size == 2 * in_size)
+            v = x >> 1;
+        else
+            v = (int)floorf((float)x * scale);
+        idx[x] = v < in_size - 1 ? v : in_size - 1;
+    }
+    return 0;
+}
+
+int l4p_instance_mask_clip(l4p_stream s, const unsigned char* src, int n_src, int in_h, int in_w, int pix_stride,
+                           const int* frame_index, const int* ytab, const int* xtab, float* mask_out, int T_out, int out_h,
+                           int out_w) {
+    if (!src || !frame_index || !ytab || !xtab || !mask_out || n_src <= 0 || in_h <= 0 || in_w <= 0 || pix_stride <= 0 ||
+        T_out <= 0 || out_h <= 0 || out_w <= 0) {
+        l4p_set_error("instance_mask_clip: bad arguments");
+        return L4P_E_INVALID;
+    }
+    hipStream_t stream = (hipStream_t)s;
+    ProfScope prof(PROF_PREP, stream, "instance_mask_clip T%d %dx%d", T_out, in_h, in_w);
+    hipLaunchKernelGGL(instance_mask_clip_kernel, dim3(grid_for((long long)T_out * out_h * out_w)), dim3(256), 0, stream, src,
+                       n_src, in_h, in_w, pix_stride, frame_index, ytab, xtab, mask_out, T_out, out_h, out_w);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+int l4p_seg_query_select(l4p_stream s, const float* mask, int h, int w, const int* cells, int M, int* sel, int* count) {
+    if (!mask || !cells || !sel || !count || h <= 0 || w <= 0 || M <= 0) {
+        l4p_set_error("seg_query_select: bad arguments");
+        return L4P_E_INVALID;
+    }
+    hipStream_t stream = (hipStream_t)s;
+    ProfScope prof(PROF_PREP, stream, "seg_query_select M%d", M);
+    hipLaunchKernelGGL(seg_query_select_kernel, dim3(1), dim3(256), 0, stream, mask, h, w, cells, M, sel, count);
     HIP_TRY(hipGetLastError());
     return 0;
 }

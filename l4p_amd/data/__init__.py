@@ -1,3 +1,5 @@
 """Caller side of the hot path: clip preparation on the GPU (mirror of the reference's l4p/data package for the
-demo's generic-video case)."""
+demo's cases: generic videos, DAVIS, DyCheck)."""
+from .davis import DavisDataset  # noqa: F401
+from .dycheck_dataset import DycheckDataset  # noqa: F401
 from .video_dataset import VideoDataset, pil_resize_blur_resize, prepare_clip  # noqa: F401

@@ -134,18 +134,110 @@ def grid_queries(spacing: float, T: int, H: int, W: int) -> torch.Tensor:
     return q
 
 
+def _index_table(fn: str, in_size: int, out_size: int) -> np.ndarray:
+    """One of the library's host index rules (l4p_pil_nearest_table / l4p_torch_nearest_table) as an int32 array."""
+    idx = np.empty(out_size, dtype=np.int32)
+    _lib.check(getattr(_lib.load(), fn)(in_size, out_size, idx.ctypes.data), fn)
+    return idx
+
+
+def mask_index_table(in_size: int, pil_size: Optional[int], res_size: int, crop0: int, out_size: int) -> np.ndarray:
+    """Source row / column of every row / column of the prepared instance mask along one axis: Pillow's NEAREST round trip
+    in_size -> pil_size -> in_size (davis.py:98-102 on a palette annotation; ``pil_size=None``: no round trip, the annotation
+    went through the bilinear passes instead), F.interpolate(mode="nearest") in_size -> res_size (l4p_dataset_mini.py:266) and
+    the crop [crop0, crop0 + out_size) (:337), composed."""
+    tab = _index_table("l4p_torch_nearest_table", in_size, res_size)[crop0:crop0 + out_size]
+    if pil_size is not None:
+        down = _index_table("l4p_pil_nearest_table", in_size, pil_size)
+        up = _index_table("l4p_pil_nearest_table", pil_size, in_size)
+        tab = down[up[tab]]
+    return np.ascontiguousarray(tab, dtype=np.int32)
+
+
+_NEAREST_MODES = ("P", "1")  # PIL.Image.resize replaces the requested filter by NEAREST for these
+_BILINEAR_MODES = ("L", "RGB")
+
+
+def instance_mask_clip(ann: torch.Tensor, mode: str, pil_size: Tuple[int, int], fidx: torch.Tensor, res_h: int, res_w: int, i0: int,
+                       j0: int, Tn: int, Hn: int, Wn: int) -> torch.Tensor:
+    """instanceseg_b1thw [1,Tn,Hn,Wn] from decoded annotation frames (uint8 [n,H,W] or [n,H,W,3], device) of PIL mode ``mode``:
+    davis.py:98-110 + mirror padding + nearest resize + centre crop in one launch (csrc/preprocess.hip)."""
+    if ann.dtype != torch.uint8 or ann.dim() not in (3, 4):
+        raise ValueError("annotations must be uint8 [T,H,W] or [T,H,W,C]")
+    if ann.dim() == 3:
+        ann = ann[..., None]
+    ann = ann.contiguous()
+    n, H, W, c = ann.shape
+    pw, ph = int(pil_size[0]), int(pil_size[1])
+    if mode in _NEAREST_MODES:
+        ytab, xtab = mask_index_table(H, ph, res_h, i0, Hn), mask_index_table(W, pw, res_w, j0, Wn)
+    elif mode in _BILINEAR_MODES:
+        ann = pil_resize_blur_resize(ann, (pw, ph))  # the round trip really is bilinear: the integer passes, 1 or 3 channels
+        ytab, xtab = mask_index_table(H, None, res_h, i0, Hn), mask_index_table(W, None, res_w, j0, Wn)
+    else:
+        raise NotImplementedError(f"annotation mode {mode!r}: palette ('P', '1') and 8-bit ('L', 'RGB') annotations are implemented")
+    dev = ann.device
+    out = torch.empty((1, Tn, Hn, Wn), dtype=torch.float32, device=dev)
+    yt, xt = torch.from_numpy(ytab).to(dev), torch.from_numpy(xtab).to(dev)
+    _lib.check(_lib.load().l4p_instance_mask_clip(_stream(), _p(ann), n, H, W, c, _p(fidx), _p(yt), _p(xt), _p(out), Tn, Hn, Wn),
+               "l4p_instance_mask_clip")
+    return out
+
+
+_cells: Dict[Tuple[float, str], torch.Tensor] = {}
+
+
+def seg_cells(spacing: float) -> torch.Tensor:
+    """(x_id, y_id) of every grid candidate as sample_tracks looks it up in the eroded mask (l4p_dataset_mini.py:458-459:
+    int(g * 224) on the float32 grid value, the literal 224 whatever the crop is); int32 [M,2]."""
+    g = torch.arange(0, 1, spacing)
+    gx, gy = torch.meshgrid(g, g, indexing="xy")
+    return torch.stack([(gx.reshape(-1) * 224).to(torch.int32), (gy.reshape(-1) * 224).to(torch.int32)], dim=1).contiguous()
+
+
+def select_queries_over_seg(mask0: torch.Tensor, spacing: float) -> torch.Tensor:
+    """Indices (int64, device, ascending) of the grid candidates sample_tracks "uniform_over_seg" keeps for the prepared mask's
+    first frame [h,w] (:450-465): one launch, then ONE 4-byte copy to the host - the count is a tensor shape."""
+    dev = mask0.device
+    key = (float(spacing), str(dev))
+    cells = _cells.get(key)
+    if cells is None:
+        cells = _cells[key] = seg_cells(spacing).to(dev)
+    M = cells.shape[0]
+    h, w = mask0.shape
+    sel = torch.empty(M, dtype=torch.int32, device=dev)
+    count = torch.empty(1, dtype=torch.int32, device=dev)
+    mask0 = mask0.contiguous()
+    _lib.check(_lib.load().l4p_seg_query_select(_stream(), _p(mask0), h, w, _p(cells), M, _p(sel), _p(count)), "l4p_seg_query_select")
+    return sel[: int(count.item())].long()
+
+
 def prepare_clip(frames: torch.Tensor, crop_size: Optional[Tuple[int, int, int]], resize_size: Optional[Tuple[int, int]],
-                 max_frames: int = 192, stride: int = 1, spacing: float = 0.02, seq_name: str = "",
-                 default_sample_size: Tuple[int, int, int] = (16, 224, 224), length_multiply_of: int = 8) -> Dict[str, object]:
-    """Decoded uint8 frames [T,H,W,3] (device) -> the sample dict of VideoDataset.__getitem__ (un-batched)."""
+                 max_frames: Optional[int] = 192, stride: int = 1, spacing: float = 0.02, seq_name: str = "",
+                 default_sample_size: Tuple[int, int, int] = (16, 224, 224), length_multiply_of: int = 8, *,
+                 intrinsics: Optional[Sequence[float]] = None, extrinsics: bool = False, blur: bool = True,
+                 annotations: Optional[torch.Tensor] = None, annotation_mode: str = "P", instanceseg: bool = True,
+                 sampling: str = "uniform") -> Dict[str, object]:
+    """Decoded uint8 frames [T,H,W,3] (device) -> the sample dict of VideoDataset.__getitem__ (un-batched).
+
+    The keyword arguments are what DavisDataset / DycheckDataset add to the same flow (the defaults are VideoDataset):
+    ``max_frames=None`` keeps every frame; ``intrinsics=(fx, fy, cx, cy)`` replaces the dummy intrinsics; ``extrinsics`` adds the
+    identity extrinsics_b44t; ``blur=False`` skips the resize-blur-resize; ``annotations`` (uint8 [T,H,W] / [T,H,W,3] on the
+    device, frame for frame with ``frames``; None = all-zero mask) of PIL mode ``annotation_mode`` become instanceseg_b1thw;
+    ``instanceseg=False`` leaves that key out; ``sampling`` is the reference's track_2d_querry_sampling_version."""
+    if sampling not in ("uniform", "uniform_over_seg"):
+        raise ValueError(f"sampling version {sampling!r}")
     if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[-1] != 3:
         raise ValueError("frames must be uint8 [T,H,W,3]")
     if not frames.is_cuda:
         raise _lib.L4PHipError("prepare_clip needs the frames on the GPU (there is no CPU fallback)")
     dev = frames.device
-    frames = frames[: max_frames - 1]  # video_dataset.py:102-103: the read loop stops after max_frames - 1 frames
+    if max_frames is not None:
+        frames = frames[: max_frames - 1]  # video_dataset.py:102-103: the read loop stops after max_frames - 1 frames
+        annotations = annotations[: max_frames - 1] if annotations is not None else None
     if stride > 1:
         frames = frames[::stride]  # the blur is per frame: skipped frames need not be blurred
+        annotations = annotations[::stride] if annotations is not None else None
     frames = frames.contiguous()
     T0, H, W, _ = frames.shape
     ori_video_len = T0
@@ -160,7 +252,11 @@ def prepare_clip(frames: torch.Tensor, crop_size: Optional[Tuple[int, int, int]]
     idx = idx[:Tn]
 
     # -- dummy intrinsics (video_dataset.py:113-127) and their resize / crop updates (l4p_dataset_mini.py:281-285,379-381) --
-    intr = torch.Tensor([[min(H, W), 0, W / 2, 0], [0, min(H, W), H / 2, 0], [0, 0, 1, 0], [0, 0, 0, 1]])
+    if intrinsics is None:
+        intr = torch.Tensor([[min(H, W), 0, W / 2, 0], [0, min(H, W), H / 2, 0], [0, 0, 1, 0], [0, 0, 0, 1]])
+    else:  # dycheck_dataset.py:91-95
+        intr = torch.eye(4).to(dtype=torch.float32)
+        intr[0, 0], intr[1, 1], intr[0, 2], intr[1, 2] = (float(v) for v in intrinsics)
     intr = intr[:, :, None].repeat(1, 1, Tn).clone()
     if resize_size is not None:
         res_h, res_w = int(resize_size[0]), int(resize_size[1])
@@ -179,11 +275,12 @@ def prepare_clip(frames: torch.Tensor, crop_size: Optional[Tuple[int, int, int]]
     intr[1, 2, :] = intr[1, 2, :] - i0
 
     # -- pixels: blur passes + fused resize / crop / normalise --
-    pil_size = resize_size if resize_size is not None else (W, H)  # (the reference hands its (H, W) pair to PIL as is)
+    pil_size = resize_size if (blur and resize_size is not None) else (W, H)  # (the reference hands its (H, W) pair to PIL as is)
     used = sorted(set(idx))
     remap = {f: k for k, f in enumerate(used)}
     if len(used) < T0:
         frames = frames[torch.tensor(used, device=dev)]
+        annotations = annotations[torch.tensor(used, device=dev)] if annotations is not None else None
     # an output column only reads two columns of the blurred frame: the horizontal up-scaling pass produces just those
     xl = None
     x_cols = None
@@ -199,25 +296,45 @@ def prepare_clip(frames: torch.Tensor, crop_size: Optional[Tuple[int, int, int]]
                                                      Wn, mean, std, rows.shape[1], _p(vb), _p(vk), vks, _p(xl)),
                "l4p_clip_resize_normalize")
 
-    # -- queries and the dummy ground truth of sample_tracks (:438-495) --
-    q = grid_queries(spacing, Tn, Hn, Wn)
-    N = q.shape[0]
+    # -- instance mask (davis.py:96-110 and its share of mirror-pad / resize / crop) --
     f32 = dict(dtype=torch.float32, device=dev)
-    return {
+    seg = None
+    if instanceseg:
+        if annotations is None:
+            seg = torch.zeros((1, Tn, Hn, Wn), **f32)
+        else:
+            if annotations.shape[:3] != frames.shape[:3]:
+                raise ValueError(f"annotations {tuple(annotations.shape)} do not match the frames {tuple(frames.shape)}")
+            ann_pil = resize_size if resize_size is not None else (W, H)
+            seg = instance_mask_clip(annotations, annotation_mode, ann_pil, fidx, res_h, res_w, i0, j0, Tn, Hn, Wn)
+
+    # -- queries and the dummy ground truth of sample_tracks (:438-495) --
+    q = grid_queries(spacing, Tn, Hn, Wn).to(dev)
+    if sampling == "uniform_over_seg":
+        if seg is None:
+            raise ValueError('sampling version "uniform_over_seg" needs the instance mask')
+        if Hn < 224 or Wn < 224:  # :458-460 look the mask up at int(g * 224): out of range in the reference
+            raise ValueError(f"uniform_over_seg sampling indexes the mask on a 224 grid; the crop is {Hn}x{Wn}")
+        q = q[select_queries_over_seg(seg[0, 0], spacing)]
+    N = q.shape[0]
+    out = {
         "rgb_b3thw": rgb,
         "intrinsics_b44t": intr.to(dev),
-        "instanceseg_b1thw": torch.zeros((1, Tn, Hn, Wn), **f32),
+        # identity through mirror padding and the temporal crop (dycheck_dataset.py:99-100, l4p_dataset_mini.py:175-184, 338-347)
+        **({"extrinsics_b44t": torch.eye(4)[:, :, None].repeat(1, 1, Tn).to(dev)} if extrinsics else {}),
+        **({"instanceseg_b1thw": seg} if seg is not None else {}),
         "track_2d_traj_bn2t": torch.zeros((N, 2, Tn), **f32),
         "track_2d_vis_bn1t": torch.zeros((N, 1, Tn), dtype=torch.bool, device=dev),
         "track_2d_depth_bn1t": torch.ones((N, 1, Tn), **f32),
         "track_2d_valid_bn1t": torch.zeros((N, 1, Tn), dtype=torch.bool, device=dev),
-        "track_2d_pointquerries_bn3": q.to(dev),
+        "track_2d_pointquerries_bn3": q,
         "track_2d_pointlabels_bn": torch.ones((N,), **f32),
         "rgb_mean_b3111": torch.tensor(_MEAN, **f32)[:, None, None, None],
         "rgb_std_b3111": torch.tensor(_STD, **f32)[:, None, None, None],
         "seq_name": seq_name,
         "ori_video_len": ori_video_len,
     }
+    return out
 
 
 class VideoDataset(torch.utils.data.Dataset):
