@@ -43,7 +43,8 @@ typedef void* l4p_stream; /* hipStream_t */
 typedef struct l4p_engine l4p_engine;
 
 const char* l4p_last_error(void);
-int l4p_abi_version(void); /* 14: DAVIS / DyCheck datasets (l4p_pil_nearest_table, l4p_torch_nearest_table, l4p_instance_mask_clip,
+int l4p_abi_version(void); /* 15: l4p_conv3d_subpixel, knob dpt_fold_rn (dpt.<task>.fold{i}.w / .b);
+                              * 14: DAVIS / DyCheck datasets (l4p_pil_nearest_table, l4p_torch_nearest_table, l4p_instance_mask_clip,
                               * l4p_seg_query_select); 13: the 2D result video (l4p_vis_stats, l4p_vis_panels, l4p_vis_track_prep, l4p_vis_track_raster);
                               * 12: every launcher switch is a knob; 11: 4D reconstruction (l4p_recon_cameras, l4p_point_map,
                               * l4p_track_point_map, l4p_recon_track_prep, l4p_recon_track_scale, l4p_recon_trails);
@@ -67,6 +68,13 @@ int l4p_stream_destroy(l4p_stream stream);
  *                loader (l4p_gemm_desc.ups_hi) where the shape allows - the same result bit for bit, 822 MB per head never written,
  *                but MEASURED SLOWER (round 5: head conv 2190 -> 3404 us against 290 us of up-sampling saved: with one pass of four
  *                taps in flight - all the registers the kernel has left - the taps' latency is not hidden); 0 = up-sample, then convolve
+ *   "dpt_fold_rn" (L4P_DPT_FOLD_RN, default 1): l4p_dpt_forward runs the up-scaling ConvTranspose of a level and the 3x3x3 conv behind it
+ *                (act{i}.1 -> rn{i}, dpt_block.py:255-276: no non-linearity between them) as ONE sub-pixel conv over the token grid
+ *                (l4p_conv3d_subpixel with the weights dpt.<task>.fold{i}.w / .b that packing.py folds once) where those weights are
+ *                bound and the shape qualifies: a fifth of the multiply-adds, the up-scaled intermediate never exists, one weight and
+ *                one activation rounding fewer; 0 = ConvTranspose, then conv.  Equal to rounding, not bit for bit.  1 folds the levels
+ *                whose three axes are all up-scaled (the flow / depth / mask heads: c3 70.47 -> 67.92 ms per step); 2 also the camray
+ *                head's k = (2, 1, 1) levels, which keep 2/3 of the multiply-adds (measured 32 us of the step: within run-to-run noise).
  *   "ln_tracks"  (L4P_LN_TRACKS, default 1): the tracker's key LayerNorms (l4p_layernorm_res / l4p_layernorm_chain with a positional
  *                addend of period P = add_mod over whole tracks) run laid out by TOKEN: a wave owns one token and walks its tracks,
  *                the shared float rows stay in registers and the parameter vectors in LDS (bit-identical to the row kernels;
@@ -243,6 +251,22 @@ int l4p_gemm(l4p_stream stream, int dtype, const l4p_gemm_desc* d);
 #define L4P_GEMM_GROUP_MAX 4
 int l4p_gemm_group(l4p_stream stream, int dtype, const l4p_gemm_desc* d, int n);
 int l4p_conv3d_k3(l4p_stream stream, int dtype, const l4p_gemm_desc* d);
+/* Sub-pixel conv: nn.ConvTranspose3d with kernel == stride == (kt, kh, kw) followed by nn.Conv3d 3x3x3, pad 1, no bias
+ * (dpt_block.py:255-276: act_postprocess[i][1] -> scratch.layer_rn[i]) as one implicit GEMM over the LOW-resolution grid.
+ *   A       channels-last [B][Ti][Hi][Wi][Cin] T;  M = B*Ti*Hi*Wi
+ *   out_T   channels-last [B][Ti*kt][Hi*kh][Wi*kw][Cout] T (out_relu_T, optional: relu of the same values, same addressing)
+ *   N       kt*kh*kw*Cout: column n = s*Cout + f, s = (s_t*kh + s_h)*kw + s_w the position of the output voxel inside its cell
+ *   W       [N][ldw] T.  Along an axis of stride k the three conv taps of position k*i + s reach the cells {i-1, i} (s = 0),
+ *           {i, i+1} (s = k-1), {i} (0 < s < k-1) or {i-1, i, i+1} (k = 1).  Row n holds, for the active cells of its
+ *           sub-position in ascending (c_t, c_h, c_w) order, the Cin-vector  sum over the taps d that land in the cell of
+ *           W_conv[f][:][d] x W_convT[:][:][sub-tap]^T;  the rest of the row (ldw >= 2^#(k>1) * 3^#(k==1) * Cin) is never read
+ *           past the last active cell's k-tiles rounded up to the kernel's look-ahead, and is zero.  K is ignored.
+ *   bias    float [27][Cout] or NULL: row (c_t*3 + c_h)*3 + c_w, c = 0 / 1 / 2 where the output position p has p-1 outside the
+ *           up-scaled grid / both neighbours inside / p+1 outside: the sum of W_conv[f][:][d] x b_convT over the taps d inside.
+ * Cells outside the grid (the batch boundaries included) contribute zero.  A column tile contracts only its sub-position's
+ * cells, in that fixed order: deterministic sums.  Requires Cin % 64 (16-bit) / % 32 (f32), Cout % 128, every up-scaled axis
+ * >= 2 long; no residual, activation, split-K, row map.  All three engines.  packing.py fold_convT_rn builds W and bias. */
+int l4p_conv3d_subpixel(l4p_stream stream, int dtype, const l4p_gemm_desc* d);
 
 /* Row LayerNorm of a float [M][C] stream -> T and/or float.  Replaces nn.LayerNorm
  * (modeling_finetune.py:212,235; l4p_videomae.py:115,177; sam/transformer.py:143-153) and

@@ -29,7 +29,7 @@ int launch_layernorm_res(int dtype, const float* x, int x_mod, const void* delta
 extern "C" {
 
 const char* l4p_last_error(void) { return g_err; }
-int l4p_abi_version(void) { return 14; }
+int l4p_abi_version(void) { return 15; }
 
 // A HIP stream whose kernels run on CUs [first_cu, first_cu + n_cus) only (hipExtStreamCreateWithCUMask): the sharded long-video path
 // gives the tracker's latency-bound kernel chain a slice of the chip of its own, beside the chip-filling decoders on the rest.
@@ -70,6 +70,13 @@ int l4p_conv3d_k3(l4p_stream stream, int dtype, const l4p_gemm_desc* d) {
         return L4P_E_INVALID;
     }
     return launch_gemm(dtype, 1, *d, (hipStream_t)stream);
+}
+int l4p_conv3d_subpixel(l4p_stream stream, int dtype, const l4p_gemm_desc* d) {
+    if (!d) {
+        l4p_set_error("l4p_conv3d_subpixel: null descriptor");
+        return L4P_E_INVALID;
+    }
+    return launch_gemm(dtype, 2, *d, (hipStream_t)stream);
 }
 int l4p_layernorm(l4p_stream stream, int dtype, const float* x, const float* gamma, const float* beta, float eps,
                   void* out_T, float* out_f32, int M, int C) {

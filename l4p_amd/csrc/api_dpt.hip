@@ -120,6 +120,41 @@ struct Ctx {
         if (!rc) rc = launch_gemm(dt, 0, p, st);
         return o;
     }
+    // ConvTranspose3d kernel == stride == k followed by the bias-free 3x3x3 conv, folded at pack time into one sub-pixel conv over
+    // the low-resolution grid (l4p_conv3d_subpixel; weights fold{i}.w / fold{i}.b, packing.py fold_convT_rn)
+    bool fold_fits(const Vol& x, const char* wk, const char* bk, int cout, const int k[3]) {
+        // knob 1: levels whose three axes are all up-scaled (>= 8 sub-positions: a fifth to a third of the multiply-adds); 2: every
+        // up-scaling level - the camray head's k = (2, 1, 1) keeps 2/3 of them and measured 85 + 150 us against 105 + 163 us per step
+        const int kv = knob(KNOB_DPT_FOLD_RN);
+        if (dry || !kv || (kv < 2 && k[0] * k[1] * k[2] < 8) || !e->find(pre + wk) || !e->find(pre + bk)) return false;
+        return x.c % (128 / es) == 0 && cout % 128 == 0 && k[0] * k[1] * k[2] <= 64 && x.t * k[0] >= 2 && x.h * k[1] >= 2 && x.w * k[2] >= 2;
+    }
+    Vol fold(const Vol& x, const char* wk, const char* bk, int cout, const int k[3], Vol* relu_copy) {
+        Vol o = vol(x.t * k[0], x.h * k[1], x.w * k[2], cout);
+        if (relu_copy) *relu_copy = vol(o.t, o.h, o.w, cout);
+        if (rc || dry) return o;
+        GemmParams p;
+        memset(&p, 0, sizeof(p));
+        p.A = x.p;
+        p.W = W(wk);
+        p.ldw = (long long)(k[0] == 1 ? 3 : 2) * (k[1] == 1 ? 3 : 2) * (k[2] == 1 ? 3 : 2) * x.c;
+        p.M = (int)x.vox(B);
+        p.N = k[0] * k[1] * k[2] * cout;
+        p.K = (int)p.ldw;
+        p.Ti = x.t;
+        p.Hi = x.h;
+        p.Wi = x.w;
+        p.Cin = x.c;
+        p.bias = (const float*)W(bk);
+        p.out_T = o.p;
+        p.out_relu_T = relu_copy ? relu_copy->p : nullptr;
+        p.kt = k[0];
+        p.kh = k[1];
+        p.kw = k[2];
+        p.Cout = cout;
+        if (!rc) rc = launch_gemm(dt, 2, p, st);
+        return o;
+    }
     // 3x3x3 conv, pad 1; optional bias / ReLU output / two T residuals / relu copy
     // ups_h / ups_w > 0: the conv reads x up-sampled (bilinear, align_corners) to ups_h x ups_w, formed in its loader
     Vol conv3(const Vol& x_in, const char* wk, const char* bk, int cout, const int s[3], int act, const void* r1, const void* r2,
@@ -191,6 +226,15 @@ int run(Ctx& c, const l4p_dpt_cfg* cfg, const void* const* hooks, float* out) {
         snprintf(bk, sizeof(bk), "act%d.1.b", i);
         if (sf[0] > 0 || sf[1] > 0 || sf[2] > 0) {
             const int k[3] = {1 << sf[0], 1 << sf[1], 1 << sf[2]};
+            // knob dpt_fold_rn: one sub-pixel conv in place of the two (the workspace is sized for the unfolded form, which needs
+            // more: the knob may change between sizing and a forward)
+            char fw[32], fb[32];
+            snprintf(fw, sizeof(fw), "fold%d.w", i);
+            snprintf(fb, sizeof(fb), "fold%d.b", i);
+            if (c.fold_fits(a, fw, fb, F, k)) {
+                lay[i] = c.fold(a, fw, fb, F, k, &layr[i]);
+                continue;
+            }
             a = c.convT(a, wk, bk, cfg->layer_dims[i], k);
         } else if (sf[0] < 0 || sf[1] < 0 || sf[2] < 0) {
             const int s[3] = {1 << -sf[0], 1 << -sf[1], 1 << -sf[2]};

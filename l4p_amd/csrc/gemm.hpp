@@ -807,6 +807,129 @@ __device__ __forceinline__ void gemm_epilogue_convt(const GemmParams& p, f32x4 (
     }
 }
 
+// ---- sub-pixel conv (l4p_conv3d_subpixel, include/l4p_hip.h): ConvTranspose3d with kernel == stride == k folded into the 3x3x3 conv
+//      behind it (packing.py fold_convT_rn).  Output column n = s * Cout + f, s = (s_t * kh + s_h) * kw + s_w the sub-position of the
+//      up-scaled voxel inside its low-resolution cell.  Along an axis the three taps of position k i + s reach the cells
+//      {i-1, i} (s = 0), {i, i+1} (s = k - 1), {i} (in between) or {i-1, i, i+1} (k = 1), so a column tile - which lies inside ONE
+//      sub-position: Cout is a multiple of the tile width - contracts only those cells, in ascending (c_t, c_h, c_w) order, Cin
+//      channels each: its weight rows hold exactly that sequence.  A cell is a tap of the 27-tap low-resolution neighbourhood, so the
+//      loaders' validity masks and tap offsets serve unchanged. ----
+struct SubpixCells {
+    int t0, h0, w0;  // first cell of each axis as a tap coordinate (0 .. 2 = cell offset -1 .. +1)
+    int nh, nw, n;   // cells along h and w, cells in all
+};
+__device__ __forceinline__ void subpix_axis(int k, int s, int& c0, int& nc) {
+    if (k == 1)
+        c0 = 0, nc = 3;
+    else if (s == 0)
+        c0 = 0, nc = 2;
+    else if (s == k - 1)
+        c0 = 1, nc = 2;
+    else
+        c0 = 1, nc = 1;
+}
+__device__ __forceinline__ SubpixCells subpix_cells(const GemmParams& p, int n0) {  // (n0: wave uniform)
+    const int s = n0 / p.Cout;
+    SubpixCells c;
+    int nt;
+    subpix_axis(p.kt, s / (p.kw * p.kh), c.t0, nt);
+    subpix_axis(p.kh, (s / p.kw) % p.kh, c.h0, c.nh);
+    subpix_axis(p.kw, s % p.kw, c.w0, c.nw);
+    c.n = nt * c.nh * c.nw;
+    return c;
+}
+// tap (0 .. 26) of the j-th active cell; j past the end repeats the last one (loaders that run ahead mask those tiles out)
+__device__ __forceinline__ int subpix_tap(const SubpixCells& c, int j) {
+    j = j < c.n ? j : c.n - 1;
+    const int r = j / c.nw;
+    return (c.t0 + r / c.nh) * 9 + (c.h0 + r % c.nh) * 3 + c.w0 + j % c.nw;
+}
+
+// Epilogue of the sub-pixel conv: the L4P_EPI_CONVT scatter (pixel shuffle) + the border-class bias row + the optional relu copy.
+// p.bias is a table [27][Cout]: row ((c_t * 3 + c_h) * 3 + c_w), c = 0 / 1 / 2 where the up-scaled position p has p - 1 outside the
+// grid / both neighbours inside / p + 1 outside (the ConvTranspose bias exists inside the up-scaled grid and is zero in the conv's
+// padding; every up-scaled axis is at least 2 long - checked by the launcher - so the three cases are exclusive).  The interior row
+// is fetched once per lane; a border row of the tile fetches its own.
+template <typename T, int TM, int TN>
+__device__ __forceinline__ void gemm_epilogue_subpixel(const GemmParams& p, f32x4 (&acc)[TM][TN], int m_wave0, int n_wave0, int li, int kg) {
+    constexpr int ES = sizeof(T), NV = 4 * TN, NG = NV / 8;
+    const int nb = n_wave0 + NV * kg;
+    const int s = n_wave0 / p.Cout, co = nb - s * p.Cout;  // (a wave's columns lie inside one sub-position: Cout % tile width == 0)
+    const int s_w = s % p.kw, s_h = (s / p.kw) % p.kh, s_t = s / (p.kw * p.kh);
+    const int To = p.Ti * p.kt, Ho = p.Hi * p.kh, Wo = p.Wi * p.kw;
+    const long long coff = (((long long)s_t * Ho + s_h) * Wo + s_w) * p.Cout + co;
+    float bv[NV];
+#pragma unroll
+    for (int c = 0; c < NV; c += 4) {
+        const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+        const f32x4 b4 = p.bias ? *(const f32x4*)(p.bias + 13 * p.Cout + co + c) : z;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) bv[c + q] = b4[q];
+    }
+    const bool pow2 = ((p.Wi & (p.Wi - 1)) | (p.Hi & (p.Hi - 1)) | (p.Ti & (p.Ti - 1))) == 0;
+    const int sw = __builtin_ctz(p.Wi), sh = __builtin_ctz(p.Hi), st = __builtin_ctz(p.Ti);
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+        const int m = m_wave0 + i * 16 + li;
+        if (m >= p.M) continue;
+        int wi, hi, ti, b;
+        if (pow2) {
+            wi = m & (p.Wi - 1);
+            hi = (m >> sw) & (p.Hi - 1);
+            ti = (m >> (sw + sh)) & (p.Ti - 1);
+            b = m >> (sw + sh + st);
+        } else {
+            wi = m % p.Wi;
+            int r = m / p.Wi;
+            hi = r % p.Hi;
+            r /= p.Hi;
+            ti = r % p.Ti;
+            b = r / p.Ti;
+        }
+        const int pt = ti * p.kt + s_t, ph = hi * p.kh + s_h, pw = wi * p.kw + s_w;
+        const int cls = ((pt == 0 ? 0 : pt == To - 1 ? 2 : 1) * 3 + (ph == 0 ? 0 : ph == Ho - 1 ? 2 : 1)) * 3 + (pw == 0 ? 0 : pw == Wo - 1 ? 2 : 1);
+        float v[NV];
+        if (p.bias && cls != 13) {
+            const float* bp = p.bias + cls * p.Cout + co;
+#pragma unroll
+            for (int c = 0; c < NV; c += 4) {
+                const f32x4 b4 = *(const f32x4*)(bp + c);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) v[c + q] = acc[i][c / 4][q] + b4[q];
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < NV; ++c) v[c] = acc[i][c / 4][c % 4] + bv[c];
+        }
+        const long long off = ((((long long)b * To + pt - s_t) * Ho + (ph - s_h)) * Wo + (pw - s_w)) * p.Cout + coff;
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            const float* vv = v + 8 * g;
+            if (ES == 2) {
+                if (p.out_relu_T) {
+                    vec8h<T> o;
+#pragma unroll
+                    for (int q = 0; q < 8; ++q) o[q] = (T)fmaxf(vv[q], 0.f);
+                    *(vec8h<T>*)((T*)p.out_relu_T + off + 8 * g) = o;
+                }
+                vec8h<T> o;
+#pragma unroll
+                for (int q = 0; q < 8; ++q) o[q] = (T)vv[q];
+                *(vec8h<T>*)((T*)p.out_T + off + 8 * g) = o;
+            } else {
+                if (p.out_relu_T) {
+                    float* op = (float*)p.out_relu_T + off + 8 * g;
+                    *(f32x4*)op = (f32x4){fmaxf(vv[0], 0.f), fmaxf(vv[1], 0.f), fmaxf(vv[2], 0.f), fmaxf(vv[3], 0.f)};
+                    *(f32x4*)(op + 4) = (f32x4){fmaxf(vv[4], 0.f), fmaxf(vv[5], 0.f), fmaxf(vv[6], 0.f), fmaxf(vv[7], 0.f)};
+                }
+                float* op = (float*)p.out_T + off + 8 * g;
+                *(f32x4*)op = (f32x4){vv[0], vv[1], vv[2], vv[3]};
+                *(f32x4*)(op + 4) = (f32x4){vv[4], vv[5], vv[6], vv[7]};
+            }
+        }
+    }
+}
+
 // the plain dense family (activation x residual kind); false = a combination that has no lean body.  Host-side twin of the
 // condition: dense_epilogue_is_lean() in gemm_launch.inc.
 template <typename T, int TM, int TN, class RowMap>
@@ -858,10 +981,12 @@ __device__ __forceinline__ bool gemm_epilogue_dense_dispatch(const GemmParams& p
 //  gemm_group_kernel for up to four problems in ONE launch, see below)
 // GROUPW: row-grouped weights (l4p_gemm_desc.w_gr): the tile's row group selects the weight matrix and the bias row.  Its own
 // instantiation - the descriptor is copied and patched per workgroup, which the plain kernels must not pay for.
-template <typename T, int BM, int BN, int WM, int WN, int MODE, bool GLDS, int STAGES = 2, bool GROUPW = false>
+// SUBPIX (MODE 1, LDS-DMA): the sub-pixel conv (see subpix_cells above): the k-loop walks the active cells of the tile's sub-position.
+template <typename T, int BM, int BN, int WM, int WN, int MODE, bool GLDS, int STAGES = 2, bool GROUPW = false, bool SUBPIX = false>
 __device__ __forceinline__ void gemm_body(const GemmParams& p_in, const int wg_index) {
     static_assert(STAGES == 2 || (STAGES >= 3 && STAGES <= 5 && GLDS), "deeper pipelines need LDS-DMA staging");
     static_assert(!GROUPW || MODE == 0, "row-grouped weights: dense GEMM");
+    static_assert(!SUBPIX || (MODE == 1 && GLDS && STAGES == 2), "sub-pixel conv: the LDS-DMA conv form");
     GemmParams patched;
     const GemmParams* pp = &p_in;
     if constexpr (GROUPW) {
@@ -959,8 +1084,10 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p_in, const int wg_i
         w_base[i] = (const T*)p.W + (long long)n * p.ldw + cs_w[i] * EPC;
     }
 
-    const int nk = (p.K + BK - 1) / BK;
     const int kpc = (MODE == 1) ? (p.Cin / BK) : 1;  // k-tiles per conv tap
+    SubpixCells cells{};
+    if constexpr (SUBPIX) cells = subpix_cells(p, n0);
+    const int nk = SUBPIX ? cells.n * kpc : (p.K + BK - 1) / BK;
 
     u32x4 ra[A_IT], rw[W_IT];
 
@@ -1024,9 +1151,13 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p_in, const int wg_i
     typedef const __attribute__((address_space(1))) void* gptr_t;
     typedef __attribute__((address_space(3))) void* lptr_t;
     // conv position of the LDS-DMA stream (see issue_tile); starts at this workgroup's first k-tile (split-K: not 0)
-    int cp_kt = 0, cp_tap = 0, cp_ci0 = 0;
+    // (SUBPIX: cp_tap counts the active cells, cp_bit is the current cell's tap)
+    int cp_kt = 0, cp_tap = 0, cp_ci0 = 0, cp_bit = 0;
     long long cp_off = 0;
-    if (MODE == 1) {
+    if constexpr (SUBPIX) {
+        cp_bit = subpix_tap(cells, 0);
+        cp_off = (((long long)(cp_bit / 9 - 1) * p.Hi + ((cp_bit / 3) % 3 - 1)) * p.Wi + (cp_bit % 3 - 1)) * p.Cin;
+    } else if (MODE == 1) {
         const int nsp = p.splitk > 1 ? p.splitk : 1;
         cp_kt = (int)((long long)nk * ksplit / nsp);
         cp_tap = cp_kt / kpc;
@@ -1056,11 +1187,12 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p_in, const int wg_i
                 if (cp_ci0 == p.Cin) {
                     cp_ci0 = 0;
                     ++cp_tap;
-                    const int tp = cp_tap < 27 ? cp_tap : 26;
+                    const int tp = SUBPIX ? subpix_tap(cells, cp_tap) : (cp_tap < 27 ? cp_tap : 26);
+                    if constexpr (SUBPIX) cp_bit = tp;
                     cp_off = (((long long)(tp / 9 - 1) * p.Hi + ((tp / 3) % 3 - 1)) * p.Wi + (tp % 3 - 1)) * p.Cin;
                 }
             }
-            const int tap = cp_tap;
+            const int tap = SUBPIX ? cp_bit : cp_tap;
             const long long toff = cp_off + cp_ci0;
 #pragma unroll
             for (int i = 0; i < A_IT; ++i) {
@@ -1217,6 +1349,10 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p_in, const int wg_i
         if (STAGES == 2) __syncthreads();
     }
 
+    if constexpr (SUBPIX) {
+        gemm_epilogue_subpixel<T, TM, TN>(p, acc, m0 + wm * (TM * 16), n0 + wn * (TN * 16), li, kg);
+        return;
+    }
     if (p.splitk > 1) {
         // raw float partial [ksplit][M][N]; bias / activation / residuals / conversion happen in splitk_finish_kernel
         const int nb2 = n0 + wn * (TN * 16) + 4 * TN * kg;
@@ -1242,9 +1378,9 @@ __device__ __forceinline__ void gemm_body(const GemmParams& p_in, const int wg_i
     gemm_epilogue<T, TM, TN>(p, acc, m0 + wm * (TM * 16), n0 + wn * (TN * 16), li, kg);
 }
 
-template <typename T, int BM, int BN, int WM, int WN, int MODE, bool GLDS, int STAGES = 2, bool GROUPW = false>
+template <typename T, int BM, int BN, int WM, int WN, int MODE, bool GLDS, int STAGES = 2, bool GROUPW = false, bool SUBPIX = false>
 __global__ __launch_bounds__(WM* WN * 64) void gemm_kernel(const GemmParams p) {
-    gemm_body<T, BM, BN, WM, WN, MODE, GLDS, STAGES, GROUPW>(p, (int)blockIdx.x);
+    gemm_body<T, BM, BN, WM, WN, MODE, GLDS, STAGES, GROUPW, SUBPIX>(p, (int)blockIdx.x);
 }
 
 // Up to L4P_GEMM_GROUP_MAX independent dense GEMMs as ONE launch: workgroups [first[g], first[g + 1]) run problem g.  For the

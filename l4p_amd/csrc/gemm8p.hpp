@@ -45,9 +45,13 @@ struct Gemm8pCfg {
 // pointers of the next tile live only across those six stage calls (they are recomputed at the top of the next iteration from an
 // opaque copy of the tile origin): the epilogue's register budget is unchanged.  Matters most where tiles are short: the mask
 // product (K = 352: 5.5 k-tiles per tile, 48 - 96 tiles per CU).
-template <typename T, int MODE, int WR, int WC, bool SPLITK = false, int TM = 8, int TN = 4, bool PERSIST = false>
+// SUBPIX (MODE 1 without split-K): the sub-pixel conv (gemm.hpp, subpix_cells): the k-tile sequence of a tile is the active cells of its
+// sub-position x Cin / 64 channel slices - the staging counters step through those cells, the phases are untouched - and the epilogue is
+// gemm_epilogue_subpixel.
+template <typename T, int MODE, int WR, int WC, bool SPLITK = false, int TM = 8, int TN = 4, bool PERSIST = false, bool SUBPIX = false>
 __global__ __launch_bounds__(512) void gemm8p_kernel(const GemmParams p) {
     static_assert(!PERSIST || (MODE == 0 && !SPLITK), "persistent form: dense GEMM without split-K");
+    static_assert(!SUBPIX || (MODE == 1 && !SPLITK && !PERSIST), "sub-pixel conv: the conv form without split-K");
     static_assert(WR * WC == 8 && (WC == 2 || WC == 4), "8 waves");
     static_assert(TM % 2 == 0 && TN % 2 == 0 && (WR * TM) % 8 == 0, "half tiles; A half-tile = whole 64-row staging passes");
     constexpr int BM = WR * TM * 16, BN = WC * TN * 16, BK = 64;
@@ -188,10 +192,12 @@ __global__ __launch_bounds__(512) void gemm8p_kernel(const GemmParams p) {
     };
     setup_src(m0, n0);
 
-    const int nk_all = (p.K + BK - 1) / BK;
+    const int kpc = (MODE == 1) ? (p.Cin / BK) : 1;
+    SubpixCells cells{};
+    if constexpr (SUBPIX) cells = subpix_cells(p, n0);
+    const int nk_all = SUBPIX ? cells.n * kpc : (p.K + BK - 1) / BK;
     const int kt0 = SPLITK ? (int)((long long)nk_all * ksplit / nsplit) : 0;
     const int nk = SPLITK ? (int)((long long)nk_all * (ksplit + 1) / nsplit) - kt0 : nk_all;
-    const int kpc = (MODE == 1) ? (p.Cin / BK) : 1;
     const char* zero = (const char*)g_zero_chunk;
 
     // Conv (MODE 1): k-tile kt is (tap kt / kpc, channel slice kt % kpc).  Both A streams (h = 0, 1) are staged in
@@ -201,6 +207,7 @@ __global__ __launch_bounds__(512) void gemm8p_kernel(const GemmParams p) {
     struct ConvPos {
         int kt, tap, ci0;
         long long off;  // byte offset of (tap, ci0) relative to the lane's centre voxel
+        int bit;        // SUBPIX: tap counts the active cells, bit is the current cell's tap
     } cpos[2];
     auto conv_tap_off = [&](int tap) {
         const int dt = tap / 9 - 1, dh = (tap / 3) % 3 - 1, dw = tap % 3 - 1;
@@ -208,7 +215,10 @@ __global__ __launch_bounds__(512) void gemm8p_kernel(const GemmParams p) {
     };
     if (MODE == 1) {
 #pragma unroll
-        for (int h = 0; h < 2; ++h) cpos[h] = ConvPos{0, 0, 0, conv_tap_off(0)};
+        for (int h = 0; h < 2; ++h) {
+            const int first = SUBPIX ? subpix_tap(cells, 0) : 0;
+            cpos[h] = ConvPos{0, 0, 0, conv_tap_off(first), first};
+        }
     }
     auto stage_a = [&](int h, int kt, int buf) {
         long long off;
@@ -223,10 +233,15 @@ __global__ __launch_bounds__(512) void gemm8p_kernel(const GemmParams p) {
                 if (c.ci0 == p.Cin) {
                     c.ci0 = 0;
                     ++c.tap;
-                    c.off = conv_tap_off(c.tap < 27 ? c.tap : 26);
+                    if constexpr (SUBPIX) {
+                        c.bit = subpix_tap(cells, c.tap);
+                        c.off = conv_tap_off(c.bit);
+                    } else {
+                        c.off = conv_tap_off(c.tap < 27 ? c.tap : 26);
+                    }
                 }
             }
-            tap = c.tap;
+            tap = SUBPIX ? c.bit : c.tap;
             off = c.off + (long long)c.ci0 * 2;
         }
 #pragma unroll
@@ -388,7 +403,9 @@ __global__ __launch_bounds__(512) void gemm8p_kernel(const GemmParams p) {
     return;
 #endif
     // (the mask-product epilogue exists for the 8 x 4 wave tile only - launch_gemm never sends it to another form)
-    if (TN == 4 && p.epi == EPI_MASKDOT) {
+    if constexpr (SUBPIX) {
+        gemm_epilogue_subpixel<T, TM, TN>(p, acc, m0 + wr * (TM * 16), n0 + wc * (TN * 16), li, kg);
+    } else if (TN == 4 && p.epi == EPI_MASKDOT) {
         if constexpr (TN == 4) gemm_epilogue_maskdot<T, TM, TN>(p, acc, m0 + wr * (TM * 16), n0 + wc * (TN * 16), li, kg);
     } else if (!gemm_epilogue_dense_dispatch<T, TM, TN>(p, acc, m0 + wr * (TM * 16), n0 + wc * (TN * 16), li, kg)) {
         // (the generic row body - every scatter form, row map and residual kind decided at run time - is compiled into the 8 x 4

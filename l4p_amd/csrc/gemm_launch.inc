@@ -112,6 +112,18 @@ static int launch_8p_form(const GemmParams& p, hipStream_t stream, int grid) {
     HIP_TRY(hipGetLastError());
     return 0;
 }
+// sub-pixel conv on the 8-phase kernel (l4p_conv3d_subpixel).  K of the tag = mean executed K of the launch: 2 M N K = executed FLOPs
+static int launch_8p_subpixel(const GemmParams& p, hipStream_t stream, int mean_k) {
+    typedef Gemm8pCfg<2, 4, 8, 4> Cfg;
+    const int ntm = (p.M + Cfg::BM - 1) / Cfg::BM, ntn = p.N / Cfg::BN;
+    auto kern = gemm8p_kernel<GEMM_T, 1, 2, 4, false, 8, 4, false, true>;
+    static lds_attr_state attr_done;
+    HIP_TRY(lds_attr_once(attr_done, kern, (int)Cfg::LDS_BYTES));
+    ProfScope prof(PROF_CONV3D, stream, "M%d N%d K%d epi%d act%d subpix 8p t%dx%d", p.M, p.N, mean_k, L4P_EPI_CONVT, p.act, Cfg::BM, Cfg::BN);
+    hipLaunchKernelGGL(kern, dim3(ntm * ntn), dim3(512), Cfg::LDS_BYTES, stream, p);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
 template <int MODE, int WR, int WC, bool SPLITK = false, int TM = 8, int TN = 4>
 static int launch_8p(const GemmParams& p, hipStream_t stream) {
     typedef Gemm8pCfg<WR, WC, TM, TN> Cfg;
@@ -324,7 +336,37 @@ int GEMM_FN(int mode, const GemmParams& p_in, hipStream_t stream) {
     if (maskdot_valu) p.tuning |= 4;
     return GEMM_FN_impl(mode, p, stream);
 }
+// Sub-pixel conv (l4p_conv3d_subpixel; arguments checked by launch_gemm): the 8-phase form where 256 x 256 tiles fill the chip - the
+// dense decoders' levels 0 and 1 at batch 4: 32 x 32 and 32 x 8 tiles - else 128 x 128 tiles (gemm_variant: 1 = never 8-phase, 10 = always)
+static int launch_subpixel(const GemmParams& p, hipStream_t stream) {
+    int cells = 0, min_cells = 27;
+    for (int s = 0; s < p.kt * p.kh * p.kw; ++s) {
+        const int ks[3] = {p.kt, p.kh, p.kw}, ss[3] = {s / (p.kw * p.kh), (s / p.kw) % p.kh, s % p.kw};
+        int n = 1;
+        for (int a = 0; a < 3; ++a) n *= ks[a] == 1 ? 3 : (ss[a] == 0 || ss[a] == ks[a] - 1) ? 2 : 1;
+        cells += n;
+        min_cells = n < min_cells ? n : min_cells;
+    }
+    const int mean_k = (int)((long long)cells * p.Cin / (p.kt * p.kh * p.kw));
+#ifdef GEMM_HAS_8P
+    const int variant = knob(KNOB_GEMM_VARIANT);
+    const long long t8 = (long long)((p.M + 255) / 256) * (p.N / 256);
+    if (p.Cout % 256 == 0 && p.Cin % 64 == 0 && min_cells * (p.Cin / 64) >= 2 && variant != 1 && (variant == 10 || t8 >= 256))
+        return launch_8p_subpixel(p, stream, mean_k);
+#endif
+    constexpr int BM = 128, BN = 128;
+    const int ntm = (p.M + BM - 1) / BM, ntn = p.N / BN;
+    const size_t lds = 2 * (BM + BN) * 128;
+    auto kern = gemm_kernel<GEMM_T, BM, BN, 2, 2, 1, true, 2, false, true>;
+    static lds_attr_state attr_done;
+    HIP_TRY(lds_attr_once(attr_done, kern, (int)lds));
+    ProfScope prof(PROF_CONV3D, stream, "M%d N%d K%d epi%d act%d subpix t%dx%d", p.M, p.N, mean_k, L4P_EPI_CONVT, p.act, BM, BN);
+    hipLaunchKernelGGL(kern, dim3(ntm * ntn), dim3(256), lds, stream, p);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
 static int GEMM_FN_impl(int mode, const GemmParams& p, hipStream_t stream) {
+    if (mode == 2) return launch_subpixel(p, stream);
     if (p.kw_cols > 0) {  // block-structured weights (l4p_gemm_desc.kw_cols): the LDS-staged kernels, whose k-tile range is per tile
         if (mode != 0 || p.w_gr > 0 || p.splitk > 1 || p.relu_in || p.kw_cols % 128 || p.kw_len < 1 || p.K % 8) {
             l4p_set_error("l4p_gemm: kw_cols needs a dense GEMM without split-K / row groups, kw_cols a multiple of 128");

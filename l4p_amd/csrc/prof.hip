@@ -50,6 +50,7 @@ const KnobDef kKnobs[KNOB_NUM] = {{"conv_halo", "L4P_CONV_HALO", 1}, {"gemm_4w",
                                    {"fc2_splitk8", "L4P_FC2_SPLITK8", -1},
                                    {"enc_defer_res", "L4P_ENC_DEFER_RES", 1},
                                    {"enc_sk_in_ln", "L4P_ENC_SK_IN_LN", 1},
+                                   {"dpt_fold_rn", "L4P_DPT_FOLD_RN", 1},
                                    {"probe_kernels", "", 0}};
 std::atomic<int> g_knob[KNOB_NUM];
 std::once_flag g_knob_once;

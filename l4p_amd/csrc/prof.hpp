@@ -31,6 +31,8 @@ enum Knob {
     KNOB_GEMM_PERSIST, KNOB_SKINNY_MAX_M, KNOB_GEMM_DEEP, KNOB_GEMM_GROUP, KNOB_EPI_GENERIC, KNOB_GEMM_VARIANT, KNOB_GEMM_T192,
     // attention.hip, dpt_ops.hip, api.hip
     KNOB_ATTN_PERSIST, KNOB_ATTN_VARIANT, KNOB_UPS_IPT, KNOB_UPS_NT, KNOB_FC2_SPLITK8, KNOB_ENC_DEFER_RES, KNOB_ENC_SK_IN_LN,
+    // api_dpt.hip
+    KNOB_DPT_FOLD_RN,
     KNOB_PROBE_KERNELS, KNOB_NUM
 };
 int knob(int id);

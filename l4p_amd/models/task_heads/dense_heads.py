@@ -17,6 +17,7 @@ from typing import Dict, List, Optional, Sequence, Tuple
 import torch
 
 from ... import ops
+from ... import _lib
 from ..._lib import ACT_NONE, ACT_RELU
 from ...weights import ModelCfg, actpost_of, fusion_of
 from ..aligner import LstSqAffineAligner, LinearAligner, WindowOverlapAligner
@@ -55,6 +56,14 @@ def dpt_decode(W, cfg: ModelCfg, task: str, hooks: Sequence[torch.Tensor], out_c
         a = a.view(B, nt, nh, nw, Li)
         sf = ap[i]
         if any(s > 0 for s in sf):
+            k = tuple(2 ** s for s in sf)
+            # knob dpt_fold_rn (csrc/api_dpt.hip, fold_fits): ConvTranspose + rn as one sub-pixel conv where the folded weights exist
+            kv = _lib.load().l4p_get_knob(b"dpt_fold_rn")
+            if (kv and (kv >= 2 or k[0] * k[1] * k[2] >= 8) and pre + f"fold{i}.w" in W and pre + f"fold{i}.b" in W
+                    and Li % (128 // a.element_size()) == 0 and F_ % 128 == 0 and k[0] * k[1] * k[2] <= 64
+                    and nt * k[0] >= 2 and nh * k[1] >= 2 and nw * k[2] >= 2):
+                layers.append(ops.conv3d_subpixel(a, Wt(f"fold{i}.w"), F_, k, bias_cls=Wt(f"fold{i}.b"), relu_copy=True))
+                continue
             a = ops.conv_transpose(a, Wt(f"act{i}.1.w"), Li, tuple(2 ** s for s in sf), bias_taps=Wt(f"act{i}.1.b"))
         elif any(s < 0 for s in sf):
             a = ops.conv3d_k3(a, Wt(f"act{i}.1.w"), Li, stride=tuple(2 ** (-s) for s in sf), bias=Wt(f"act{i}.1.b"))

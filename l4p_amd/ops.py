@@ -219,6 +219,30 @@ def conv3d_k3(x: torch.Tensor, w: torch.Tensor, cout: int, *, stride: Tuple[int,
     return (out, out_relu) if relu_copy else out
 
 
+def conv3d_subpixel(x: torch.Tensor, w: torch.Tensor, cout: int, k: Tuple[int, int, int], bias_cls: Optional[torch.Tensor] = None,
+                    relu_copy: bool = False):
+    """ConvTranspose3d (kernel == stride == k) followed by a bias-free 3x3x3 conv, pad 1, as one sub-pixel conv over the
+    low-resolution grid (l4p_conv3d_subpixel): x [B,Ti,Hi,Wi,Cin] -> [B,Ti*kt,Hi*kh,Wi*kw,cout].  w, bias_cls: packing.fold_convT_rn
+    ([kt*kh*kw*cout][cells*Cin] engine dtype, float [27][cout])."""
+    dtype = code_of(x.dtype)
+    B, Ti, Hi, Wi, Cin = x.shape
+    kt, kh, kw = k
+    out = torch.empty((B, Ti * kt, Hi * kh, Wi * kw, cout), dtype=x.dtype, device=x.device)
+    assert w.dtype == x.dtype and w.shape[0] >= kt * kh * kw * cout
+    d = GemmDesc()
+    d.A, d.W, d.ldw = _p(x), _p(w), w.shape[1]
+    d.M, d.N, d.K = B * Ti * Hi * Wi, kt * kh * kw * cout, w.shape[1]
+    d.Ti, d.Hi, d.Wi, d.Cin = Ti, Hi, Wi, Cin
+    d.bias = _p(bias_cls)
+    d.out_T = _p(out)
+    out_relu = torch.empty_like(out) if relu_copy else None
+    d.out_relu_T = _p(out_relu)
+    d.kt, d.kh, d.kw, d.Cout = kt, kh, kw, cout
+    lib = _lib.load()
+    _lib.check(lib.l4p_conv3d_subpixel(_stream(), dtype, C.byref(d)), "l4p_conv3d_subpixel")
+    return (out, out_relu) if relu_copy else out
+
+
 def conv_transpose(x: torch.Tensor, w: torch.Tensor, cout: int, k: Tuple[int, int, int],
                    bias_taps: Optional[torch.Tensor] = None, act: int = ACT_NONE) -> torch.Tensor:
     """ConvTranspose3d with kernel == stride == k, channels-last.  w: [ceil128(taps*cout)][Cin], row = tap*cout+co;

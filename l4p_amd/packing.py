@@ -9,6 +9,8 @@ Layouts (T = engine dtype, bf16 or f32; "rows" are padded with zeros to a multip
   Conv3d 3x3x3 [Co,Ci,3,3,3]         -> [rows(Co)][27*Ci] (k = tap*Ci + ci, tap = (dt*3+dh)*3+dw)
   Conv3d 1x1x1 [Co,Ci,1,1,1]         -> [rows(Co)][Ci]
   ConvTranspose3d k==s [Ci,Co,k...]  -> [rows(taps*Co)][Ci] (row = tap*Co + co), bias repeated per tap
+  ConvTranspose3d k==s -> Conv3d 3x3x3 (DPT act_postprocess[i][1] -> layer_rn[i]) additionally folded into ONE sub-pixel conv:
+                                     -> [taps*Co][cells*Ci] + border-class bias table [27][Co] f32 (fold_convT_rn)
   biases, LayerNorm affine, embeddings, pos table, tiny output convs                      f32
 """
 from __future__ import annotations
@@ -55,6 +57,72 @@ def convT_matrix(w: torch.Tensor) -> torch.Tensor:
     ci, co = w.shape[:2]
     taps = w.shape[2] * w.shape[3] * w.shape[4]
     return w.permute(2, 3, 4, 1, 0).reshape(taps * co, ci)
+
+
+def fold_axis_cells(k: int, s: int) -> List[int]:
+    """Low-resolution cell offsets that the three conv taps of up-scaled position k*i + s reach along one axis."""
+    return sorted({(s + d) // k for d in (-1, 0, 1)})
+
+
+def fold_max_cells(k: Tuple[int, int, int]) -> int:
+    """Most active cells of any sub-position: the common row stride of the folded weights is fold_max_cells(k) * Ci."""
+    return int(np.prod([3 if ka == 1 else 2 for ka in k]))
+
+
+def fold_bias_class(p: int, n: int) -> int:
+    """Border class of position p on an up-scaled axis of length n >= 2, from which of p-1, p, p+1 lie inside the grid:
+    0 = p-1 outside, 1 = both neighbours inside, 2 = p+1 outside."""
+    lo, hi = p - 1 >= 0, p + 1 < n
+    if lo and hi:
+        return 1
+    if not lo and not hi:
+        raise ValueError("an up-scaled axis of length 1 has no border class of the [27] table")
+    return 2 if lo else 0
+
+
+def fold_convT_rn(w_ct: torch.Tensor, b_ct: torch.Tensor, w_rn: torch.Tensor, dtype=torch.float64):
+    """ConvTranspose3d (kernel == stride == k; w_ct [L, Mid, kt, kh, kw], b_ct [Mid]) followed by Conv3d 3x3x3, pad 1, no bias
+    (w_rn [F, Mid, 3, 3, 3]) is one linear map: a conv over the LOW-resolution grid with kt*kh*kw*F output channels that are
+    pixel-shuffled to the up-scaled grid.  Along an axis, tap d of up-scaled position p = k*i + s reads position k*i + s + d, i.e.
+    cell i + (s + d) // k at sub-tap (s + d) % k, so sub-position s = (s_t*kh + s_h)*kw + s_w and cell offset c = (c_t, c_h, c_w) meet
+        Wc[s][c] = sum_{taps d : cell(s + d) = c}  W_rn[:, :, d] @ W_ct[:, :, sub(s + d)]^T            [F x L]
+    and most (s, c) pairs are structurally zero (fold_axis_cells).  Returns
+      w     [kt*kh*kw*F][fold_max_cells(k)*L]: row s*F + f holds the ACTIVE cells of s in ascending (c_t, c_h, c_w), L channels each,
+            zero behind them (what l4p_conv3d_subpixel reads),
+      bias  [27][F]: the ConvTranspose bias exists inside the up-scaled grid and is zero in the conv's padding, so an output
+            receives sum_{taps inside} W_rn[:, :, d] @ b_ct: row (c_t*3 + c_h)*3 + c_w of the per-axis classes of fold_bias_class,
+      nblk  the number of active (sub-position, cell) blocks.
+    Formed in ``dtype`` (float64) from the un-rounded weights; the caller rounds once to the engine type."""
+    L, mid = w_ct.shape[:2]
+    k = tuple(int(x) for x in w_ct.shape[2:])
+    F_ = w_rn.shape[0]
+    wc, wr = w_ct.to(dtype), w_rn.to(dtype)
+    ksub, stride = k[0] * k[1] * k[2], fold_max_cells(k) * L
+    w = torch.zeros(ksub, F_, stride, dtype=dtype)
+    subs = [(st, sh, sw) for st in range(k[0]) for sh in range(k[1]) for sw in range(k[2])]
+    cells = [[(ct, ch, cw) for ct in fold_axis_cells(k[0], st) for ch in fold_axis_cells(k[1], sh) for cw in fold_axis_cells(k[2], sw)]
+             for st, sh, sw in subs]
+    nblk = sum(len(c) for c in cells)
+    wc_all = wc.permute(1, 2, 3, 4, 0).reshape(mid, ksub * L)  # [Mid][(sub-tap, l)]
+    for dt in (-1, 0, 1):
+        for dh in (-1, 0, 1):
+            for dw in (-1, 0, 1):
+                # tap d against every sub-tap at once: [F][sub-tap][L]; sub-position s takes its sub-tap's slice into its cell's block
+                pd = (wr[:, :, dt + 1, dh + 1, dw + 1] @ wc_all).view(F_, ksub, L)
+                for s, (st, sh, sw) in enumerate(subs):
+                    c = ((st + dt) // k[0], (sh + dh) // k[1], (sw + dw) // k[2])
+                    sub = (((st + dt) % k[0]) * k[1] + (sh + dh) % k[1]) * k[2] + (sw + dw) % k[2]
+                    j = cells[s].index(c)
+                    w[s, :, j * L:(j + 1) * L] += pd[:, sub, :]
+    w = w.reshape(ksub * F_, stride)
+    v = torch.einsum("fmtuv,m->tuvf", wr, b_ct.to(dtype))  # per-tap bias contribution [3][3][3][F]
+    bias = torch.zeros(3, 3, 3, F_, dtype=dtype)
+    keep = {0: (1, 2), 1: (0, 1, 2), 2: (0, 1)}  # taps (as indices 0..2) inside the grid per class
+    for ct in range(3):
+        for ch in range(3):
+            for cw in range(3):
+                bias[ct, ch, cw] = v[list(keep[ct])][:, list(keep[ch])][:, :, list(keep[cw])].sum((0, 1, 2))
+    return w, bias.reshape(27, F_), nblk
 
 
 class Packer:
@@ -119,6 +187,11 @@ def pack_dpt(pk: Packer, sd: Dict[str, torch.Tensor], c: ModelCfg, task: str):
             taps = w.shape[2] * w.shape[3] * w.shape[4]
             pk.T(f"{o}act{i}.1.w", convT_matrix(w))
             pk.F(f"{o}act{i}.1.b", sd[a + "1.bias"].repeat(taps))
+            # ... and the same ConvTranspose folded into the 3x3x3 conv behind it (knob dpt_fold_rn; the unfolded entries stay: the
+            # knob's other setting and shapes the sub-pixel kernel does not take)
+            fw, fb, _ = fold_convT_rn(w, sd[a + "1.bias"], sd[f"{p}scratch.layer_rn.{i}.weight"])
+            pk.T(f"{o}fold{i}.w", fw)
+            pk.F(f"{o}fold{i}.b", fb)
         elif any(x < 0 for x in sf):
             pk.T(f"{o}act{i}.1.w", conv3_matrix(sd[a + "1.weight"]))
             pk.F(f"{o}act{i}.1.b", sd[a + "1.bias"])
