@@ -137,7 +137,16 @@ const char* l4p_prof_class_name(int cls);
 int l4p_prof_read(int cls, double* total_ms, long long* count);
 /* Per-(class, tag) breakdown (tag = GEMM shape, LayerNorm shape, kernel name ...) of the same event pairs as text
  * lines "class\ttag\tcount\ttotal_ms\n", largest first.  Returns the bytes needed incl. the terminator; writes at
- * most cap bytes to buf (buf may be NULL to query the size).  Tuning aid behind tools/prof_detail.py. */
+ * most cap bytes to buf (buf may be NULL to query the size).  Tuning aid behind tools/prof_detail.py.
+ * Tags of the attention class (l4p_attention): "B<B> S<S> H<H> Dh<Dh> <form>", at most 63 characters; <form> names the kernel
+ * the launcher chose:
+ *   "rows64"          the 64-row kernel (csrc/attention64.hip; knob "attn64")
+ *   "qsplit persist"  the 8-wave query-split kernel, 256 persistent workgroups that walk the tiles
+ *   "qsplit pertile"  the same kernel, one workgroup per tile (knob "attn_persist" = 0, or no more than 256 tiles)
+ *   "kvsplit"         the 8-wave KV-split kernel (too few tiles for two workgroups per CU)
+ *   "unsplit"         the 4-wave kernel, one workgroup per 128 query rows
+ *   "kvsplit cs" / "unsplit cs"  the same two with the compiler-scheduled body (knob "attn_variant" = 1)
+ *   "f32"             the f32 engine's kernel */
 long long l4p_prof_detail(char* buf, long long cap);
 
 /* ------------------------------------------------------------------------------------------------
@@ -277,8 +286,9 @@ int l4p_layernorm(l4p_stream stream, int dtype, const float* x, const float* gam
 /* Fused softmax(q k^T * scale) v for the encoder (modeling_finetune.py:180-186).
  * q: [B*S][H*96] T, kt: tiled K, vt: [B][H][96][S] T (all three written by L4P_EPI_QKV), out: [B*S][H*Dh] T.
  * Dh in {88, 64} (head dim < 96: the padding carries the softmax denominator (V^T) and the running maximum (Q, K)).
- * scale > 0: q is the plain projection; the bf16 kernel folds scale * log2(e) into its Q fragments (a second bf16
- * rounding of q).  scale == 0 (L4P_ATTN_PRESCALED): q was already multiplied by head_dim^-0.5 * log2(e) when it was
+ * scale > 0: q is the plain projection; the f16 kernel folds scale * log2(e) into its Q fragments (a second f16
+ * rounding of q), the bf16 engine runs the compiler-scheduled body ("kvsplit cs" / "unsplit cs" below), which applies
+ * the scale in float to the scores - a second bf16 rounding of q would cost percents on peaked rows.  scale == 0 (L4P_ATTN_PRESCALED): q was already multiplied by head_dim^-0.5 * log2(e) when it was
  * produced (l4p_gemm_desc.q_scale) and the weights are exp2(q k^T) — the form the engine uses: one rounding of q. */
 #define L4P_ATTN_PRESCALED 0.0f
 int l4p_attention(l4p_stream stream, int dtype, const void* q, const void* kt, const void* vt, void* out, int B, int S,

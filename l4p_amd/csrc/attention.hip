@@ -710,7 +710,12 @@ static int launch_attn_t(const void* q, const void* kt, const void* vt, void* ou
     HIP_TRY(lds_attr_once(attr_done, kern, (int)lds));
     // scale == 0 (L4P_ATTN_PRESCALED): q already carries head_dim^-0.5 * log2(e); the kernels then multiply by exactly 1
     const float c_scale = scale > 0.f ? scale * 1.4426950408889634f : 1.0f;
-    ProfScope prof(PROF_ATTENTION, stream);
+    // which form ran (include/l4p_hip.h, at l4p_prof_detail): the tests assert it; formatted only while profiling is on
+    const char* form = sizeof(T) == 4 ? "f32"
+                       : QS > 1       ? (grid < ntiles ? "qsplit persist" : "qsplit pertile")
+                       : SPLIT > 1    ? (HS ? "kvsplit" : "kvsplit cs")
+                                      : (HS ? "unsplit" : "unsplit cs");
+    ProfScope prof(PROF_ATTENTION, stream, "B%d S%d H%d Dh%d %s", B, S, H, DH, form);
     hipLaunchKernelGGL(kern, dim3(grid), dim3(256 * SPLIT * QS), lds, stream, (const T*)q, (const T*)kt, (const T*)vt, (T*)out,
                        S, H, c_scale, ntiles);
     HIP_TRY(hipGetLastError());
@@ -746,7 +751,12 @@ int launch_attention(int dtype, const void* q, const void* kt, const void* vt, v
     }
     // too few workgroups for two per CU (256 CUs): split the KV range over two wave groups inside each workgroup
     const bool split = (long long)(S / 128) * H * B < 512 && (S / 64) % 2 == 0;
-    const int variant = knob(KNOB_ATTN_VARIANT);  // tuning aid: 1 = compiler-scheduled body
+    int variant = knob(KNOB_ATTN_VARIANT);  // tuning aid: 1 = compiler-scheduled body
+    // bf16 with the scale inside: the hand-scheduled bodies fold scale * log2(e) into their Q fragments, a second bf16 rounding of
+    // q (2^-9 per element) that shifts the scores of a large-norm query row against large-norm keys by a few percent of a unit -
+    // measured 2.7e-2 of max|out| on a row of 8x norm against keys of 6x norm.  The compiler-scheduled body applies the scale in
+    // float to the accumulated scores.  (The engine passes pre-scaled q and is not affected.)
+    if (dtype == L4P_BF16 && scale > 0.f) variant = 1;
     // chip-filling 16-bit launches: one wave per SIMD, 64 query rows per wave (attention64.hip)
     if (is16(dtype) && variant == 0 && knob(KNOB_ATTN64) && S % 256 == 0 && (S / 64) % 2 == 0 && S / 64 >= 4 && (long long)(S / 256) * H * B >= 256)
         return launch_attention64(dtype, q, kt, vt, out, B, S, H, Dh, scale, stream);

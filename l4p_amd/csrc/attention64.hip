@@ -572,7 +572,7 @@ static int launch_attn64_t(const void* q, const void* kt, const void* vt, void* 
     const int ntiles = (S / 256) * H * B;
     const int grid = ntiles > 256 ? 256 : ntiles;
     const size_t lds = 2 * (size_t)(12288 + 12288) + (size_t)256 * 96 * 2;
-    ProfScope prof(PROF_ATTENTION, stream);
+    ProfScope prof(PROF_ATTENTION, stream, "B%d S%d H%d Dh%d rows64", B, S, H, Dh);
     if (Dh == 88) {
         auto kern = attn64::attn64_kernel<T, 88>;
         static lds_attr_state attr_done;

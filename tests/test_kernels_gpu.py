@@ -141,9 +141,9 @@ LOG2E = 1.4426950408889634
 
 
 def check_attn(out, ref, mode, prescaled):
-    """Attention outputs.  Pre-scaled q (the engine's form): the file's bf16-output bound.  scale applied inside the bf16
-    kernel: q * scale * log2(e) is rounded to bf16 a second time in registers, which perturbs every score by ~2^-9
-    relative — bound 1.5x looser (rel-L2 4.5e-3, 2 ulp of the maximum)."""
+    """Attention outputs.  Pre-scaled q (the engine's form): the file's bf16-output bound.  scale applied inside a 16-bit
+    kernel: bound 1.5x looser (rel-L2 4.5e-3, 2 bf16 ulp of the maximum) - the hand-scheduled body (f16) rounds
+    q * scale * log2(e) to the storage type a second time in registers; bf16 runs the body that scales in float."""
     if prescaled or mode == L4P_F32:
         return check(out, ref, mode, True)
     y = out.float().cpu()
@@ -154,7 +154,8 @@ def check_attn(out, ref, mode, prescaled):
 
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("prescaled", [True, False])
-@pytest.mark.parametrize("B,S,H,Dh", [(1, 2048, 16, 88), (2, 256, 2, 88), (1, 128, 3, 64)])
+@pytest.mark.parametrize("B,S,H,Dh", [(1, 2048, 16, 88), (2, 256, 2, 88), (1, 128, 3, 64),
+                                      (1, 384, 2, 88), (1, 384, 3, 64)])  # S % 256 != 0: K tile order and V^T at six KV blocks
 def test_qkv_attention(dev, mode, prescaled, B, S, H, Dh):
     """qkv GEMM epilogue layouts (q dense — optionally pre-multiplied by head_dim^-0.5 log2 e as the engine does —, k in
     tile order, v transposed) + fused attention vs softmax(q k^T / sqrt(d)) v."""
@@ -235,11 +236,15 @@ def test_attention_peaked_softmax(dev, mode, prescaled, S, B, H):
                                       (3, 2048, 16, 88),   # 384 tiles: workgroups with one and with two tiles
                                       (11, 1024, 6, 88),   # 264 tiles of 16 KV blocks, batch * heads = 66 not a multiple of 8 (plain tile order)
                                       (4, 2048, 16, 64),   # head dim 64: the constant pieces sit elsewhere in the tile
-                                      (16, 256, 16, 88)])  # the shortest sequence the kernel takes: 4 KV blocks, every step is a first / last one
+                                      (16, 256, 16, 88),   # the shortest sequence the kernel takes: 4 KV blocks, every step is a first / last one
+                                      (8, 1024, 16, 88)])  # 512 tiles: with attn64 = 0 the 8-wave query-split kernel (persistent, two tiles per workgroup)
 def test_attention64_forms_and_the_8_wave_kernel(dev, knob, mode, B, S, H, Dh):
     """csrc/attention64.hip (one wave per SIMD, 64 query rows per wave; launches of >= 256 tiles of 256 rows) against fp32 softmax
-    on the same rounded operands, in its tile-walk variants, and against the 8-wave kernel on the same inputs (knob attn64 = 0):
-    the two agree to the rounding of P - they move the deferred maximum per 64 / per 32 rows."""
+    on the same rounded operands, in its tile-walk variants, and against the kernel the launcher picks for the same inputs with knob
+    attn64 = 0: the 8-wave query-split kernel at >= 512 tiles of 256 rows and head dim 88 (the last shape), the 4-wave unsplit
+    kernel at every other shape here (fewer tiles, or head dim 64).  The two agree to the rounding of P - they move the deferred
+    maximum per 64 / per 32 rows.  Both launches assert their kernel form through the profiler tag."""
+    from tests.test_gemm8p_gpu import prof_tags
     g = torch.Generator().manual_seed(B * 1000 + S + Dh)
     q4 = torch.randn(B, S, H, ops.DP, generator=g) * (Dh ** -0.5 * LOG2E)
     k4 = torch.randn(B, S, H, ops.DP, generator=g)
@@ -249,10 +254,13 @@ def test_attention64_forms_and_the_8_wave_kernel(dev, knob, mode, B, S, H, Dh):
     k4[1, S - 120:S - 112] *= 5.0  # a few dominant keys in one batch item: the rescale path runs in some waves and not in others
     q, kt, vt, qf, kf, vf = _attn_inputs(q4, k4, v4, mode)
     out = {}
+    other = "qsplit persist" if Dh == 88 and (S // 256) * H * B >= 512 else "unsplit"
     for v in (1, 0):
         knob("attn64", v)
-        out[v] = ops.attention(q, kt, vt, Dh, scale=0.0)
-        torch.cuda.synchronize()
+        with prof_tags() as p:
+            out[v] = ops.attention(q, kt, vt, Dh, scale=0.0)
+        tags = [ln[1] for ln in p.lines if ln[0] == "attention"]
+        assert tags == [f"B{B} S{S} H{H} Dh{Dh} {'rows64' if v else other}"], p.lines
     td = ops.torch_dtype(mode)
     ref = torch.empty(B, S, H, Dh)
     for b in range(B):  # (per batch item: the fp32 score matrix of one item is 16 x 2048 x 2048 floats)
@@ -288,6 +296,14 @@ def test_attention_very_negative_and_huge_scores(dev, mode):
     out = ops.attention(q, kt, vt, Dh)
     assert bool(torch.isfinite(out.float()).all())
     check_attn(out, ref, mode, False)
+    # the same rows with q pre-scaled (the engine's form; for bf16 the only one that runs the deferred-maximum body)
+    q, kt, vt, qf, kf, vf = _attn_inputs(q4 * (Dh ** -0.5 * LOG2E), k4, v4, mode)
+    qh, kh, vh = (t.permute(0, 2, 1, 3).double() for t in (qf, kf, vf))
+    attn = torch.softmax((qh * math.log(2.0)) @ kh.transpose(-2, -1), dim=-1)
+    ref = (attn @ vh)[..., :Dh].transpose(1, 2).reshape(B * S, H * Dh).float()
+    out = ops.attention(q, kt, vt, Dh, scale=0.0)
+    assert bool(torch.isfinite(out.float()).all())
+    check_attn(out, ref, mode, True)
 
 
 @pytest.mark.parametrize("mode", MODES)
