@@ -3,12 +3,15 @@ sections 1 / 3) or DycheckDataset (--dycheck, section 5: the camera file's intri
 DataLoader(batch_size=1) -> prepare_model(...).forward(batch, tasks).  The outputs are reported (and optionally saved as .npz).
 --vis DIR writes the reference's side-by-side result video (generate_video_visualizations, demo.py:78,113: RGB, depth, flow, motion
 mask, track trails) rendered on the GPU; --recon4d DIR adds the camray task and writes the 4D reconstruction of the reference's 4D
-sections (generate_4D_visualization, demo.py:116-258) as PLY files under DIR.  The viser viewer stays out of scope.
+sections (generate_4D_visualization, demo.py:116-258) as PLY files under DIR; --view4d DIR adds the camray task too and renders what
+those sections end in (visualize_point_cloud_viser, demo.py:151-160: the point cloud of frame t, track trails and camera frustum from a
+free viewpoint) on the GPU, along an orbit camera path, as a video under DIR.
 
   python demo/demo.py --videos a.mp4 b.mp4 --ckpt weights/l4p_depth_flow_2d3dtrack_camray_dynseg_v1.ckpt   # needs mediapy
   python demo/demo.py --synthetic                      # no checkpoint / video files here: seeded weights + a seeded video
   python demo/demo.py --synthetic --vis out/           # + the five-panel result video (.mp4 with mediapy, PNG frames without)
   python demo/demo.py --synthetic --recon4d out/       # + 4D point clouds / track trails / frusta as PLY under out/
+  python demo/demo.py --synthetic --view4d out/        # + the 4D result from a free viewpoint (.mp4 with mediapy, PNG frames without)
   python demo/demo.py --davis DAVIS_ROOT --ckpt ...    # JPEGImages/480p/<seq>, Annotations/480p/<seq>: queries on the instance masks
   python demo/demo.py --dycheck DYCHECK_ROOT --ckpt ... --recon4d out/   # <seq>/dense/images, <seq>/calibration.txt
   python demo/demo.py --synthetic --davis X --vis out/ # a small seeded DAVIS (or --dycheck: DyCheck) tree in a temporary directory
@@ -56,6 +59,9 @@ def parse_args(argv=None):
     ap.add_argument("--recon4d", default=None, metavar="DIR",
                     help="also run the camray task and write each video's 4D reconstruction (world point clouds, 3D track trails, "
                          "camera frusta as PLY; l4p_amd.utils.recon4d.generate_4D_visualization) under DIR")
+    ap.add_argument("--view4d", default=None, metavar="DIR",
+                    help="also run the camray task and render each video's 4D reconstruction from an orbiting viewpoint (points, track "
+                         "trails, camera frusta; l4p_amd.utils.view4d.generate_4D_video) as <seq_name>_4d under DIR")
     ap.add_argument("--precision", default="16-mixed",
                     help="engine: 16-mixed (the reference demo's own, IEEE half; default) | bf16 (what bench.py measures) | 32-true")
     args = ap.parse_args(argv)
@@ -71,10 +77,10 @@ def parse_args(argv=None):
 def plan(args):
     """(tasks, dataset keyword arguments) of the reference demo's section that ``args`` selects."""
     tasks = ["depth", "flow_2d_backward", "dyn_mask", "track_2d"]  # demo.py:82,99
-    if args.recon4d or args.dycheck:
+    if args.recon4d or args.view4d or args.dycheck:
         tasks.append("camray")  # the reference's 4D sections (demo.py:116-258) add it
     kw = dict(crop_size=(args.frames, 224, 224), estimation_directions=[1], track_2d_querry_sampling_spacing=args.spacing)
-    if args.davis and args.recon4d:
+    if args.davis and (args.recon4d or args.view4d):
         kw["crop_size"] = (56, 224, 224)  # demo.py:131
     if args.dycheck:
         kw.update(resize_size=(298, 224), stride=2)  # demo.py:216-224
@@ -157,6 +163,8 @@ def run(args, model, dataset, tasks):
             vis_2d(batch, out, tasks, args.vis)
         if args.recon4d:
             recon_4d(batch, out, tasks, args.recon4d)
+        if args.view4d:
+            view_4d(batch, out, tasks, args.view4d)
 
 
 def vis_2d(batch, out, tasks, out_dir):
@@ -200,6 +208,33 @@ def recon_4d(batch, out, tasks, out_dir):
     n = rec["points"].shape[0] + rec.get("track_xyz", rec["points"][:0]).shape[0]
     print(f"  4D: {T} frames, {n / 1e6:.2f} M points, scale {float(rec.get('scale', torch.ones(1))[0]):.4g}; "
           f"GPU reconstruction {(t1 - t0) * 1e3:.1f} ms, PLY writing {(t2 - t1) * 1e3:.0f} ms -> {path}")
+
+
+def view_4d(batch, out, tasks, out_dir):
+    """generate_4D_video split into its GPU part (reconstruction, camera path, renderer), the copy to the host and the file writing,
+    each timed on its own."""
+    from l4p_amd.utils import recon4d, view4d, vis2d
+
+    T, H, W = batch["rgb_b3thw"].shape[2:]
+    size = (480, 640)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    rec = recon4d.reconstruct_4d(batch, out, tasks)
+    path = view4d.orbit_views(rec, out["depth_est_b1thw"], T, T)
+    K = out["traj3d_intrinsics_est_b16t"].reshape(4, 4, T)[:, :, 0].float().cpu().numpy().astype(np.float64)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    res = view4d.render_4d_views(rec, T, H * W, path["cam_T_world"], view4d.scaled_intrinsics(K, (H, W), size), size, path["frames"],
+                                 tracks="track_2d" in tasks)
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    frames = res["image"].cpu().numpy()
+    t3 = time.perf_counter()
+    name = vis2d.write_video(frames, out_dir, batch["seq_name"][0] + "_4d")
+    t4 = time.perf_counter()
+    print(f"  4D view: {frames.shape[0]} views of {size[0]} x {size[1]}, look-at distance {path['d0']:.3g}; reconstruction + camera path "
+          f"{(t1 - t0) * 1e3:.1f} ms, GPU render {(t2 - t1) * 1e3:.1f} ms, copy to host {(t3 - t2) * 1e3:.1f} ms, file writing "
+          f"{(t4 - t3) * 1e3:.0f} ms -> {name}")
 
 
 if __name__ == "__main__":

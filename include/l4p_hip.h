@@ -43,7 +43,8 @@ typedef void* l4p_stream; /* hipStream_t */
 typedef struct l4p_engine l4p_engine;
 
 const char* l4p_last_error(void);
-int l4p_abi_version(void); /* 15: l4p_conv3d_subpixel, knob dpt_fold_rn (dpt.<task>.fold{i}.w / .b);
+int l4p_abi_version(void); /* 16: the free-viewpoint 4D renderer (l4p_view_splat, l4p_view_mesh, l4p_view_resolve);
+                              * 15: l4p_conv3d_subpixel, knob dpt_fold_rn (dpt.<task>.fold{i}.w / .b);
                               * 14: DAVIS / DyCheck datasets (l4p_pil_nearest_table, l4p_torch_nearest_table, l4p_instance_mask_clip,
                               * l4p_seg_query_select); 13: the 2D result video (l4p_vis_stats, l4p_vis_panels, l4p_vis_track_prep, l4p_vis_track_raster);
                               * 12: every launcher switch is a knob; 11: 4D reconstruction (l4p_recon_cameras, l4p_point_map,
@@ -475,6 +476,53 @@ int l4p_vis_track_prep(l4p_stream stream, const float* key_traj, const float* tr
 int l4p_vis_track_raster(l4p_stream stream, const int* xy, const unsigned char* vis, const float* colors, int N, int T, int H,
                          int W, int trail, const float* src, long long s_px, long long s_row, long long s_frame, void* out,
                          long long o_row, long long o_frame, int out_u8);
+
+/* ------------------------------------------------------------------------------------------------
+ * Free-viewpoint renderer of the 4D reconstruction: what the reference shows through its viser viewer (the point cloud of frame t,
+ * its track trails and the camera frustum from a camera the user moves, l4p/utils/viser.py:58-75), as depth-tested images of V
+ * views.  View v shows frame frame[v] under the f32 view matrix M = cam_T_world [V][4][4] (row-major) and the pinhole
+ * intr [V][4] = (fx, fy, cx, cy).  Its points are the dense cloud points[frame * HW + i], i in [0, HW), followed by the trail
+ * points track_xyz[off[frame] + (i - HW)], i - HW in [0, off[frame + 1] - off[frame]); i is the point's local index.
+ * zbuf [V][Ho][Wo] unsigned long long holds per pixel the smallest key (bits(z) << 32) | low: a positive f32 orders as its bit
+ * pattern, so that is the nearest surface, ties to the smallest low word; low = i for a point, 0x80000000 | (frame << 4 | tri)
+ * for a frustum triangle, all ones in an empty pixel.  The minimum does not depend on the order of arrival: the image is
+ * reproducible bit for bit (tests/view4d_restate.py restates the rules in numpy).  A view whose frame[v] is outside [0, T) stays
+ * empty; a trail block that does not lie inside track_xyz counts as empty.
+ * The viewer's own rasteriser is not restated: these rules are the project's.  Every operation rounds in f32 in the order written.
+ * ---------------------------------------------------------------------------------------------- */
+
+/* Points (viser.py:58-75, add_point_cloud with point_size).  Clears zbuf to all ones on the stream, then for every point P:
+ *   1. x = ((M00 X + M01 Y) + M02 Z) + M03, likewise y (row 1) and z (row 2);
+ *   2. skip unless x, y, z are finite and z >= near;
+ *   3. u = (fx x) / z + cx, v = (fy y) / z + cy;
+ *   4. skip unless |u| < 2^20 and |v| < 2^20;
+ *   5. px = floor(u + 0.5), py = floor(v + 0.5): pixel index = integer coordinate, as in generate_point_map;
+ *   6. h = floor(min(((point_size fx) / z) 0.5, max_half))  (min(a, b) = a if a < b else b; skip unless h >= 0);
+ *   7. the point covers the square [px - h, px + h] x [py - h, py + h], clipped to the image;
+ *   8. every covered pixel takes min(zbuf, (bits(z) << 32) | i).
+ * track_xyz / off may be NULL (or n_track = 0, the rows of track_xyz): dense points only.  HW + n_track < 2^31, max_half <= 64,
+ * near > 0, V <= 65535. */
+int l4p_view_splat(l4p_stream stream, const float* points, const float* track_xyz, const long long* off, int T, int HW,
+                   long long n_track, const float* cam_T_world, const float* intr, const int* frame, int V, int Ho, int Wo,
+                   float point_size, int max_half, float near_z, unsigned long long* zbuf);
+/* Frustum triangles into the same buffer, after the splat (viser.py:58-75, add_mesh_trimesh of the camera mesh): frustum [T][8][3]
+ * (the vertices of the recon cameras call), create_camera_frustum's 12 triangles.  View v draws the frustum of frame f = frame[v]
+ * and, with stride >= 1, of every f < frame[v] with f % stride = 0 (the camera path).  Vertices k = 0, 1, 2 go through steps 1-4
+ * (a skipped vertex skips the triangle).  With d(a, b, p) = (u_b - u_a) (p_y - v_a) - (v_b - v_a) (p_x - u_a): A = d(0, 1, P_2),
+ * a triangle with A = 0 is skipped; over the integer pixels p of [ceil(min u), floor(max u)] x [ceil(min v), floor(max v)] clipped
+ * to the image: b0 = d(1, 2, p) / A, b1 = d(2, 0, p) / A, b2 = d(0, 1, p) / A; covered when b0, b1, b2 >= 0 (two-sided, edges
+ * included); z = 1 / ((b0 / z0 + b1 / z1) + b2 / z2) (perspective-correct), kept when finite and >= near; the pixel takes
+ * min(zbuf, (bits(z) << 32) | 0x80000000 | (f << 4 | tri)).  T <= 65535. */
+int l4p_view_mesh(l4p_stream stream, const float* frustum, int T, const float* cam_T_world, const float* intr, const int* frame,
+                  int V, int Ho, int Wo, int stride, float near_z, unsigned long long* zbuf);
+/* zbuf -> image [V][Ho][Wo][3] uchar, depth [V][Ho][Wo] float (the winner's camera z, +inf where empty), index [V][Ho][Wo] int
+ * (the low word: the local point index, the triangle code with the high bit set, -1 where empty) (viser.py:58-75: what the viewer
+ * puts on the screen).  Colours: colors [T HW][3] / track_colors [n_track][3] uchar of the winning point, the background
+ * (bg_r, bg_g, bg_b) where empty, and for triangle tri the frustum colour (255, 127, 127) * shade[tri] / 32 in integers,
+ * shade = {32, 31, 18, 17, 27, 26, 23, 22, 29, 28, 21, 20}.  Same T, HW, off, n_track, frame as the splat call that filled zbuf. */
+int l4p_view_resolve(l4p_stream stream, const unsigned long long* zbuf, const unsigned char* colors, const unsigned char* track_colors,
+                     const long long* off, int T, int HW, long long n_track, const int* frame, int V, int Ho, int Wo, int bg_r,
+                     int bg_g, int bg_b, unsigned char* image, float* depth, int* index);
 
 /* ------------------------------------------------------------------------------------------------
  * SAM-style point tracker (sparse_heads.py, sam/{prompt_encoder,transformer,mask_decoder}.py).

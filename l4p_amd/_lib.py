@@ -14,7 +14,7 @@ L4P_BF16 = 0
 L4P_F32 = 1
 L4P_F16 = 2  # IEEE half storage / f16 MFMA: the arithmetic class of the reference's "16-mixed" (fp16 autocast)
 
-ABI_VERSION = 15  # what l4p_abi_version() of the library this binding was written against returns (include/l4p_hip.h)
+ABI_VERSION = 16  # what l4p_abi_version() of the library this binding was written against returns (include/l4p_hip.h)
 
 EPI_DENSE, EPI_QKV, EPI_CONVT, EPI_MASKDOT = 0, 1, 2, 3
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
@@ -132,6 +132,9 @@ SIGNATURES = {
     "l4p_vis_panels": (_I, [_VP] * 10 + [_I] * 8 + [_VP, _I, _VP, _VP]),
     "l4p_vis_track_prep": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _F, _VP, _VP, _VP, _VP]),
     "l4p_vis_track_raster": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _VP, _LL, _LL, _LL, _VP, _LL, _LL, _I]),
+    "l4p_view_splat": (_I, [_VP, _VP, _VP, _VP, _I, _I, _LL, _VP, _VP, _VP, _I, _I, _I, _F, _I, _F, _VP]),
+    "l4p_view_mesh": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _I, _I, _I, _I, _F, _VP]),
+    "l4p_view_resolve": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _LL, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP]),
     "l4p_layernorm_ex": (_I, [_VP, _I, _VP, _VP, _VP, _F, _VP, _VP, _I, _I, _VP, _I, _VP, _I]),
     "l4p_gemm_group": (_I, [_VP, _I, _VP, _I]),
     "l4p_layernorm_res": (_I, [_VP, _I, _VP, _I, _VP, _VP, _VP, _F, _VP, _VP, _I, _I, _VP, _I, _VP, _VP, _I, _I, _VP]),

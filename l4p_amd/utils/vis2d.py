@@ -252,12 +252,14 @@ def read_png_frames(directory: str) -> np.ndarray:
 
 def write_video(out_vid: np.ndarray, out_path: str, seq_name: str) -> str:
     """<out_path>/<seq_name>.mp4 at 15 fps through mediapy where it is importable (vis.py:99-100; mediapy is not installed where
-    this was written, so that branch has never run here), else the uint8 frames as PNG files under <out_path>/<seq_name>/."""
+    this was written, so that branch has never run here), else the uint8 frames as PNG files under <out_path>/<seq_name>/.  A uint8
+    video (utils/view4d.py) is written as it is."""
     os.makedirs(out_path, exist_ok=True)
     try:
         import mediapy as media
     except ImportError:
-        return write_png_frames(to_uint8(out_vid), os.path.join(out_path, seq_name))
+        frames = out_vid if np.asarray(out_vid).dtype == np.uint8 else to_uint8(out_vid)
+        return write_png_frames(frames, os.path.join(out_path, seq_name))
     name = os.path.join(out_path, f"{seq_name}.mp4")
     media.write_video(name, out_vid, fps=FPS)
     return name
