@@ -43,7 +43,9 @@ typedef void* l4p_stream; /* hipStream_t */
 typedef struct l4p_engine l4p_engine;
 
 const char* l4p_last_error(void);
-int l4p_abi_version(void); /* 16: the free-viewpoint 4D renderer (l4p_view_splat, l4p_view_mesh, l4p_view_resolve);
+int l4p_abi_version(void); /* 17: evaluation metrics (l4p_metric_ws_bytes, l4p_metric_depth, l4p_metric_flow, l4p_metric_mask,
+                              * l4p_metric_tracks, l4p_metric_cameras, l4p_select_median_dev);
+                              * 16: the free-viewpoint 4D renderer (l4p_view_splat, l4p_view_mesh, l4p_view_resolve);
                               * 15: l4p_conv3d_subpixel, knob dpt_fold_rn (dpt.<task>.fold{i}.w / .b);
                               * 14: DAVIS / DyCheck datasets (l4p_pil_nearest_table, l4p_torch_nearest_table, l4p_instance_mask_clip,
                               * l4p_seg_query_select); 13: the 2D result video (l4p_vis_stats, l4p_vis_panels, l4p_vis_track_prep, l4p_vis_track_raster);
@@ -368,6 +370,12 @@ int l4p_rays_to_pose_rot(l4p_stream stream, const float* rays, const float* R, f
 int l4p_quantile(l4p_stream stream, const float* x, long long n, float q, unsigned* ws, float* out);
 /* EXACT order statistic `rank` (0-based, ascending) of n finite floats; torch.median(x) = rank (n - 1) / 2. */
 int l4p_select_rank(l4p_stream stream, const float* x, long long n, long long rank, unsigned* ws, float* out);
+/* The lower median when the number of elements that count is known only on the device.  Per clip b of B:
+ * out[b * out_stride] = the order statistic (count[b * count_stride] - 1) / 2 of x[b][0..n), NaN when that count is 0.  x holds no
+ * NaN and +inf (the largest key) wherever an element does not count, count <= n.  The rank is written into the workspace by a small
+ * kernel from the device-side count, and the result is the selected element itself.  ws: B * L4P_QUANTILE_WS_UINTS uints. */
+int l4p_select_median_dev(l4p_stream stream, const float* x, long long n, int B, const unsigned long long* count,
+                          long long count_stride, unsigned* ws, float* out, long long out_stride);
 /* LinearAligner(method="median").solve (aligner.py:96-107): sol[0] = torch.median over f(target) / (f(pred) + 1e-8)
  * (f = safe_inverse when `inverse`, misc.py:48-62; float arithmetic; the LOWER median as torch.median returns it),
  * sol[1] = 0, so that l4p_affine_align_apply applies it.  ratios: n floats of scratch; ws >= L4P_QUANTILE_WS_UINTS uints. */
@@ -523,6 +531,68 @@ int l4p_view_mesh(l4p_stream stream, const float* frustum, int T, const float* c
 int l4p_view_resolve(l4p_stream stream, const unsigned long long* zbuf, const unsigned char* colors, const unsigned char* track_colors,
                      const long long* off, int T, int HW, long long n_track, const int* frame, int V, int Ho, int Wo, int bg_r,
                      int bg_g, int bg_b, unsigned char* image, float* depth, int* index);
+
+/* ------------------------------------------------------------------------------------------------
+ * Evaluation metrics: what a metrics_module(batch, out, metadata) of L4PLitModule.step computes (l4p/l4p.py:74-78; the reference
+ * ships none, the definitions are the benchmarks' own).  B clips per call, results as doubles on the device, nothing synchronises.
+ * Per-element arithmetic is f32, one rounding per operation in the order written (tests/metrics_restate.py restates it in numpy);
+ * sums are f64, added in a fixed order (no float atomics: a second run gives the same bits); counts are integers.  A metric whose
+ * denominator count is 0 is NaN.  Every "valid" pointer may be NULL: all valid.  Every entry refuses B < 1, n < 1, index ranges of
+ * 2^31 or more, an unknown mode and a NULL required pointer with L4P_E_INVALID and a text that names the entry.
+ * ---------------------------------------------------------------------------------------------- */
+#define L4P_DEPTH_ALIGN_NONE 0
+#define L4P_DEPTH_ALIGN_MEDIAN 1
+#define L4P_DEPTH_ALIGN_LSTSQ 2
+#define L4P_METRIC_DENSE_OUT 16   /* doubles per clip of the depth, flow and mask entries */
+#define L4P_METRIC_TRACKS_OUT 32  /* doubles per clip of the tracks entry */
+#define L4P_METRIC_TRACKS_COUNTS 18
+#define L4P_METRIC_CAMERAS_OUT 8  /* doubles per clip of the cameras entry */
+/* bytes of workspace of the depth entry for (B, n, mode); the flow and mask entries need what L4P_DEPTH_ALIGN_NONE asks for.  0 for
+ * arguments the entries refuse. */
+size_t l4p_metric_ws_bytes(int B, long long n, int mode);
+/* Depth: est, gt, valid [B][n] (n = T H W).  Element i is valid when valid > 0.5, gt is finite with dmin < gt < dmax, est is finite
+ * and > 0.  One alignment (s, t) per clip over all its frames:
+ *   L4P_DEPTH_ALIGN_NONE    (1, 0);
+ *   L4P_DEPTH_ALIGN_MEDIAN  s = the lower median (rank (c - 1) / 2 of the c valid elements, torch.median) of the f32 quotients
+ *                           gt / est, t = 0; NaN when c = 0;
+ *   L4P_DEPTH_ALIGN_LSTSQ   argmin over the valid elements of sum (s est + t - gt)^2: the sums in f64 from the f32 inputs, the 2 x 2
+ *                           normal equations solved in f64, s and t rounded to f32; NaN when c < 2 or the determinant is <= 0.
+ * Then a = min(max(s * est + t, dmin), dmax) (multiply, then add, unfused); a NaN alignment scores no element.  Per clip
+ * out[0..5] = c, sum |a - gt| / gt, sum (a - gt) * (a - gt), the counts of max(a / gt, gt / a) < 1.25f, 1.5625f, 1.953125f;
+ * out[6..10] = abs_rel, rmse (the f64 square root of the mean), delta1, delta2, delta3; out[11], out[12] = s, t.
+ * 0 < dmin < dmax.  Inverse-depth alignment and log-space errors are not provided. */
+int l4p_metric_depth(l4p_stream stream, const float* est, const float* gt, const float* valid, int B, long long n, int mode,
+                     float dmin, float dmax, void* ws, size_t ws_bytes, double* out);
+/* Optical flow: est, gt, valid [B][2][n].  An element is valid when both valid channels are > 0.5 and both gt channels are finite;
+ * epe = sqrtf(du * du + dv * dv).  out[0..4] = c, sum epe, the counts of epe < 1, 3, 5; out[5..8] = epe (mean), 1px, 3px, 5px (the
+ * shares below the threshold). */
+int l4p_metric_flow(l4p_stream stream, const float* est, const float* gt, const float* valid, int B, long long n, void* ws,
+                    size_t ws_bytes, double* out);
+/* Motion mask: logit, gt, valid [B][n].  Predicted positive is logit > 0: the reference's sigmoid(logit) > 0.5 without the rounding
+ * of the sigmoid; gt positive is gt > 0.5; over the elements with valid > 0.5: out[0..3] = TP, FP, FN, TN; out[4..8] = iou =
+ * TP / (TP + FP + FN), precision, recall, f1 = 2 TP / (2 TP + FP + FN), accuracy. */
+int l4p_metric_mask(l4p_stream stream, const float* logit, const float* gt, const float* valid, int B, long long n, void* ws,
+                    size_t ws_bytes, double* out);
+/* Tracks, the TAP-Vid measures: traj_est, traj_gt [B][N][2][T], vis_logit [B][N][T], vis_gt and valid [B][N][T] bytes (non-zero =
+ * set), queries [B][N][3] = (t + 0.5, x, y) as sample_tracks writes them.  Frame t of track i is scored when valid is set and
+ * t != floor(query t); datasets that clear valid before the query frame give TAP-Vid's "first" protocol.  Distances are taken in
+ * TAP-Vid's 256 x 256 frame: sx = 256.f / W, sy = 256.f / H, dx = (xe - xg) * sx, dy likewise, d2 = dx * dx + dy * dy, and for thr
+ * in {1, 2, 4, 8, 16} within = d2 < thr * thr; predicted visible is vis_logit > 0.  counts [B][L4P_METRIC_TRACKS_COUNTS] (workspace,
+ * cleared here) and out[0..17] = scored frames, frames with predicted == gt visibility, gt-visible frames, then per threshold:
+ * within & gt visible [3..7], TP = within & predicted visible & gt visible [8..12], FP = predicted visible & !(gt visible & within)
+ * [13..17].  out[18] = occlusion_accuracy, out[19..23] = pts_within_thr, out[24..28] = jaccard_thr = TP / (gt visible + FP),
+ * out[29] = average_pts_within_thresh, out[30] = average_jaccard (the means over the five thresholds). */
+int l4p_metric_tracks(l4p_stream stream, const float* traj_est, const float* traj_gt, const float* vis_logit,
+                      const unsigned char* vis_gt, const unsigned char* valid, const float* queries, int B, int N, int T, int H, int W,
+                      unsigned long long* counts, double* out);
+/* Cameras, ATE / RPE with the RMSE statistic: pose_est [B][16][T] row-major world_T_cam (traj3d_est_b16t), extr_gt [B][4][4][T]
+ * cam_T_world (extrinsics_b44t, inverted in f64: G).  f64 throughout.  The closed-form similarity (s, R, t) of the estimated onto
+ * the gt camera centres over all T frames (Umeyama, reflection case included, no RANSAC), then out[0] = ate = RMSE of
+ * |s R c_est + t - c_gt|; with the estimate's translations multiplied by s and E = inv(inv(G_i) G_i+1) (inv(P_i) P_i+1) for
+ * consecutive frames: out[1] = rpe_trans = RMSE of |trans(E)|, out[2] = rpe_rot = RMSE in degrees of
+ * atan2(0.5 |(E32 - E23, E13 - E31, E21 - E12)|, 0.5 (trace - 1)); out[3] = s, out[4..6] = the three sums of squares, out[7] = T.
+ * T >= 3. */
+int l4p_metric_cameras(l4p_stream stream, const float* pose_est, const float* extr_gt, int B, int T, double* out);
 
 /* ------------------------------------------------------------------------------------------------
  * SAM-style point tracker (sparse_heads.py, sam/{prompt_encoder,transformer,mask_decoder}.py).

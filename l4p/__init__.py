@@ -31,7 +31,7 @@ class _AliasFinder(importlib.abc.MetaPathFinder, importlib.abc.Loader):
         if found is None:
             raise ModuleNotFoundError(
                 f"No module named {fullname!r}: the MI355X engine (package l4p_amd, aliased as l4p) does not provide it — it "
-                "covers the inference hot path and the demo's datasets (l4p.l4p, l4p.models.*, l4p.data.video_dataset, l4p.data.davis, "
+                "covers the inference hot path and the demo's datasets (l4p.l4p, l4p.metrics, l4p.models.*, l4p.data.video_dataset, l4p.data.davis, "
                 "l4p.data.dycheck_dataset, l4p.utils.geometry_utils, l4p.utils.recon4d, l4p.utils.vis2d, l4p.utils.view4d)",
                 name=fullname)
         return importlib.util.spec_from_loader(fullname, self, is_package=found.submodule_search_locations is not None)

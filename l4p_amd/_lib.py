@@ -14,7 +14,7 @@ L4P_BF16 = 0
 L4P_F32 = 1
 L4P_F16 = 2  # IEEE half storage / f16 MFMA: the arithmetic class of the reference's "16-mixed" (fp16 autocast)
 
-ABI_VERSION = 16  # what l4p_abi_version() of the library this binding was written against returns (include/l4p_hip.h)
+ABI_VERSION = 17  # what l4p_abi_version() of the library this binding was written against returns (include/l4p_hip.h)
 
 EPI_DENSE, EPI_QKV, EPI_CONVT, EPI_MASKDOT = 0, 1, 2, 3
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
@@ -117,6 +117,7 @@ SIGNATURES = {
     "l4p_rays_to_pose_rot": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _I]),
     "l4p_quantile": (_I, [_VP, _VP, _LL, _F, _VP, _VP]),
     "l4p_select_rank": (_I, [_VP, _VP, _LL, _LL, _VP, _VP]),
+    "l4p_select_median_dev": (_I, [_VP, _VP, _LL, _I, _VP, _LL, _VP, _VP, _LL]),
     "l4p_ratio_median_solve": (_I, [_VP, _VP, _VP, _LL, _I, _VP, _VP, _VP]),
     "l4p_point_map_samples": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, C.c_uint]),
     "l4p_similarity_ransac": (_I, [_VP, _VP, _VP, _I, _VP, _F, _I, _I, C.c_uint, _VP, _VP]),
@@ -135,6 +136,12 @@ SIGNATURES = {
     "l4p_view_splat": (_I, [_VP, _VP, _VP, _VP, _I, _I, _LL, _VP, _VP, _VP, _I, _I, _I, _F, _I, _F, _VP]),
     "l4p_view_mesh": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _I, _I, _I, _I, _F, _VP]),
     "l4p_view_resolve": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _LL, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP]),
+    "l4p_metric_ws_bytes": (_SZ, [_I, _LL, _I]),
+    "l4p_metric_depth": (_I, [_VP, _VP, _VP, _VP, _I, _LL, _I, _F, _F, _VP, _SZ, _VP]),
+    "l4p_metric_flow": (_I, [_VP, _VP, _VP, _VP, _I, _LL, _VP, _SZ, _VP]),
+    "l4p_metric_mask": (_I, [_VP, _VP, _VP, _VP, _I, _LL, _VP, _SZ, _VP]),
+    "l4p_metric_tracks": (_I, [_VP] * 7 + [_I] * 5 + [_VP, _VP]),
+    "l4p_metric_cameras": (_I, [_VP, _VP, _VP, _I, _I, _VP]),
     "l4p_layernorm_ex": (_I, [_VP, _I, _VP, _VP, _VP, _F, _VP, _VP, _I, _I, _VP, _I, _VP, _I]),
     "l4p_gemm_group": (_I, [_VP, _I, _VP, _I]),
     "l4p_layernorm_res": (_I, [_VP, _I, _VP, _I, _VP, _VP, _VP, _F, _VP, _VP, _I, _I, _VP, _I, _VP, _VP, _I, _I, _VP]),

@@ -5,6 +5,7 @@
 // ground truth (tests/test_umeyama_gpu.py), not against the reference ("parity unpinned").
 #include "common.hpp"
 #include "unproject.hpp"
+#include "umeyama_moments.hpp"
 
 __device__ __forceinline__ unsigned hash_u32(unsigned x) {  // PCG-style integer hash (counter-based RNG)
     x = x * 747796405u + 2891336453u;
@@ -150,90 +151,6 @@ __global__ void pointmap_kernel(const float* __restrict__ depth, const float* __
     out[i * 3 + 0] = ox;
     out[i * 3 + 1] = oy;
     out[i * 3 + 2] = oz;
-}
-
-// -------------------------------------------------------------------------------------------------
-// Umeyama similarity from accumulated moments (skimage.transform._geometric._umeyama):
-// dst ~ s R src + t.  sums: n, mean_s[3], mean_d[3], cov[3][3] = E[(d-md)(s-ms)^T], var_s.
-// -------------------------------------------------------------------------------------------------
-__device__ void jacobi3(double A[3][3], double V[3][3]) {
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) V[i][j] = i == j;
-    for (int sweep = 0; sweep < 30; ++sweep) {
-        if (fabs(A[0][1]) + fabs(A[0][2]) + fabs(A[1][2]) < 1e-300) break;
-        for (int p = 0; p < 2; ++p)
-            for (int q = p + 1; q < 3; ++q) {
-                if (fabs(A[p][q]) < 1e-300) continue;
-                const double th = (A[q][q] - A[p][p]) / (2.0 * A[p][q]);
-                const double t = (th >= 0 ? 1.0 : -1.0) / (fabs(th) + sqrt(th * th + 1.0));
-                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
-                for (int k = 0; k < 3; ++k) {
-                    const double x = A[k][p], y = A[k][q];
-                    A[k][p] = c * x - s * y;
-                    A[k][q] = s * x + c * y;
-                }
-                for (int k = 0; k < 3; ++k) {
-                    const double x = A[p][k], y = A[q][k];
-                    A[p][k] = c * x - s * y;
-                    A[q][k] = s * x + c * y;
-                }
-                for (int k = 0; k < 3; ++k) {
-                    const double x = V[k][p], y = V[k][q];
-                    V[k][p] = c * x - s * y;
-                    V[k][q] = s * x + c * y;
-                }
-            }
-    }
-}
-
-// model: [0..8] = s*R row-major, [9..11] = t, [12] = s
-__device__ void umeyama_from_moments(const double ms[3], const double md[3], const double cov[3][3], double var_s,
-                                     float* model) {
-    double AtA[3][3], V[3][3];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) AtA[i][j] = cov[0][i] * cov[0][j] + cov[1][i] * cov[1][j] + cov[2][i] * cov[2][j];
-    jacobi3(AtA, V);
-    int o[3] = {0, 1, 2};
-    for (int a = 0; a < 2; ++a)
-        for (int b = a + 1; b < 3; ++b)
-            if (AtA[o[b]][o[b]] > AtA[o[a]][o[a]]) {
-                const int t = o[a];
-                o[a] = o[b];
-                o[b] = t;
-            }
-    double v1[3], v2[3], v3[3], u1[3], u2[3], u3[3];
-    for (int i = 0; i < 3; ++i) {
-        v1[i] = V[i][o[0]];
-        v2[i] = V[i][o[1]];
-    }
-    v3[0] = v1[1] * v2[2] - v1[2] * v2[1];
-    v3[1] = v1[2] * v2[0] - v1[0] * v2[2];
-    v3[2] = v1[0] * v2[1] - v1[1] * v2[0];
-    for (int i = 0; i < 3; ++i) {
-        u1[i] = cov[i][0] * v1[0] + cov[i][1] * v1[1] + cov[i][2] * v1[2];
-        u2[i] = cov[i][0] * v2[0] + cov[i][1] * v2[1] + cov[i][2] * v2[2];
-    }
-    const double s1 = sqrt(u1[0] * u1[0] + u1[1] * u1[1] + u1[2] * u1[2]);
-    for (int i = 0; i < 3; ++i) u1[i] /= fmax(s1, 1e-300);
-    const double dp = u1[0] * u2[0] + u1[1] * u2[1] + u1[2] * u2[2];
-    for (int i = 0; i < 3; ++i) u2[i] -= dp * u1[i];
-    const double s2 = sqrt(u2[0] * u2[0] + u2[1] * u2[1] + u2[2] * u2[2]);
-    for (int i = 0; i < 3; ++i) u2[i] /= fmax(s2, 1e-300);
-    u3[0] = u1[1] * u2[2] - u1[2] * u2[1];
-    u3[1] = u1[2] * u2[0] - u1[0] * u2[2];
-    u3[2] = u1[0] * u2[1] - u1[1] * u2[0];
-    // sigma3 with the reflection sign folded in: u3^T cov v3 (negative when det(cov) < 0)
-    double s3 = 0;
-    for (int i = 0; i < 3; ++i) s3 += u3[i] * (cov[i][0] * v3[0] + cov[i][1] * v3[1] + cov[i][2] * v3[2]);
-    const double scale = var_s > 0 ? (s1 + s2 + s3) / var_s : 1.0;
-    double R[3][3];
-    for (int i = 0; i < 3; ++i)
-        for (int j = 0; j < 3; ++j) R[i][j] = u1[i] * v1[j] + u2[i] * v2[j] + u3[i] * v3[j];
-    for (int i = 0; i < 3; ++i) {
-        for (int j = 0; j < 3; ++j) model[i * 3 + j] = (float)(scale * R[i][j]);
-        model[9 + i] = (float)(md[i] - scale * (R[i][0] * ms[0] + R[i][1] * ms[1] + R[i][2] * ms[2]));
-    }
-    model[12] = (float)scale;
 }
 
 __device__ __forceinline__ float residual(const float* m, const float* s, const float* d) {
@@ -464,6 +381,52 @@ int l4p_select_rank(l4p_stream s_, const float* x, long long n, long long rank, 
     }
     ProfScope prof(PROF_ELEMENTWISE, s, "l4p_select_rank");
     return qsel_launch(s, x, n, (unsigned)rank, 0.f, ws, out);
+}
+
+// The lower median when the number of elements that count is known only on the device: x holds +inf (the largest key) in the
+// places that do not count, so the order statistic (count - 1) / 2 of all n values is the lower median of those that do.  The
+// rank goes into the workspace from the device-side count; the result is the key of ws[0] itself (no lerp: an infinite neighbour
+// would turn it into NaN), NaN when count = 0.
+__global__ void qsel_rank_from_count_kernel(const unsigned long long* __restrict__ count, unsigned* __restrict__ ws) {
+    if (threadIdx.x != 0) return;
+    const unsigned long long c = count[0];
+    ws[0] = 0u;
+    ws[1] = c > 0 ? (unsigned)((c - 1) / 2) : 0u;
+    ws[2] = 0u;
+    ws[3] = 0xFFFFFFFFu;
+}
+__global__ void qsel_take_kernel(const unsigned* __restrict__ ws, const unsigned long long* __restrict__ count,
+                                 float* __restrict__ out) {
+    if (threadIdx.x != 0) return;
+    out[0] = count[0] > 0 ? qsel_unkey(ws[0]) : __uint_as_float(0x7FC00000u);
+}
+/* per clip b of B: out[b * out_stride] = the order statistic (count[b * count_stride] - 1) / 2 of x[b][0..n), NaN when that count
+ * is 0.  x: no NaN; count <= n.  ws: B * L4P_QUANTILE_WS_UINTS uints. */
+int l4p_select_median_dev(l4p_stream s_, const float* x, long long n, int B, const unsigned long long* count, long long count_stride,
+                          unsigned* ws, float* out, long long out_stride) {
+    hipStream_t s = (hipStream_t)s_;
+    if (B < 1 || n < 1 || n > 0x7FFFFFFFll || !x || !count || !ws || !out) {
+        l4p_set_error("l4p_select_median_dev: need B >= 1, 1 <= n < 2^31 and x, count, ws, out (B=%d n=%lld)", B, n);
+        return L4P_E_INVALID;
+    }
+    ProfScope prof(PROF_ELEMENTWISE, s, "l4p_select_median_dev");
+    HIP_TRY(hipMemsetAsync(ws, 0, (size_t)B * (4 + QSEL_BINS) * sizeof(unsigned), s));
+    const int grid = (int)((n + 255) / 256 < 256 ? (n + 255) / 256 : 256);
+    for (int b = 0; b < B; ++b) {
+        const float* xb = x + (long long)b * n;
+        unsigned* wb = ws + (long long)b * (4 + QSEL_BINS);
+        const unsigned long long* cb = count + (long long)b * count_stride;
+        hipLaunchKernelGGL(qsel_rank_from_count_kernel, dim3(1), dim3(64), 0, s, cb, wb);
+        hipLaunchKernelGGL((qsel_hist_kernel<21, 11, 0u>), dim3(grid), dim3(256), 0, s, xb, n, wb);
+        hipLaunchKernelGGL((qsel_pick_kernel<21, 11, false>), dim3(1), dim3(256), 0, s, wb);
+        hipLaunchKernelGGL((qsel_hist_kernel<10, 11, 0xFFE00000u>), dim3(grid), dim3(256), 0, s, xb, n, wb);
+        hipLaunchKernelGGL((qsel_pick_kernel<10, 11, false>), dim3(1), dim3(256), 0, s, wb);
+        hipLaunchKernelGGL((qsel_hist_kernel<0, 10, 0xFFFFFC00u>), dim3(grid), dim3(256), 0, s, xb, n, wb);
+        hipLaunchKernelGGL((qsel_pick_kernel<0, 10, true>), dim3(1), dim3(256), 0, s, wb);
+        hipLaunchKernelGGL(qsel_take_kernel, dim3(1), dim3(64), 0, s, wb, cb, out + (long long)b * out_stride);
+    }
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 // LinearAligner(method="median") (aligner.py:96-107): ratios f(target) / (f(pred) + 1e-8) in float, f = safe_inverse or identity
