@@ -333,8 +333,11 @@ __device__ __forceinline__ void gemm_epilogue_row(const GemmParams& p, float (&v
         // float residuals of the whole row segment, loaded before any of its outputs is stored (in-place updates alias)
         float rv[NV], rv2[NV];
         const bool res32 = p.res1 && p.res_f32;
+        // row of the residual: the broadcast table's, else the output's row map (l4p_gemm_desc.c_*: "rows of out / residual", as the
+        // lean bodies read it through EpiRowMapDesc)
+        const long long mres = p.res_mod > 0 ? (m % p.res_mod) : (p.c_gr > 0 ? (long long)(m / p.c_gr) * p.c_gs + p.c_go + (m % p.c_gr) : m);
         if (res32) {
-            const long long rrow = (long long)(p.res_mod > 0 ? (m % p.res_mod) : m) * p.ldr;
+            const long long rrow = mres * p.ldr;
 #pragma unroll
             for (int g8 = 0; g8 < NV; g8 += 8) {
                 const int n = nb + g8;
@@ -406,7 +409,7 @@ __device__ __forceinline__ void gemm_epilogue_row(const GemmParams& p, float (&v
                     for (int q = 0; q < 8; ++q) vv[q] += rv2[g8 + q];
                 }
             } else if (p.res1) {
-                const long long roff = (long long)(p.res_mod > 0 ? (m % p.res_mod) : m) * p.ldr + n;
+                const long long roff = mres * p.ldr + n;
                 const T* rp = (const T*)p.res1 + roff;
 #pragma unroll
                 for (int q = 0; q < 8; ++q) vv[q] += to_f32<T>(rp[q]);

@@ -222,6 +222,16 @@ static int launch_halo(const GemmParams& p, hipStream_t stream) {
 // L4P_GEMM_VARIANT (tuning aid): 1 = never use the 8-phase kernel, 10 = always.
 static int GEMM_FN_impl(int mode, const GemmParams& p, hipStream_t stream);
 int GEMM_FN(int mode, const GemmParams& p_in, hipStream_t stream);
+// block-structured weights (l4p_gemm_desc.kw_cols): what gemm_body's per-tile k-window relies on - a tile's columns lie inside one
+// column group (kw_cols a multiple of the widest tile) and the window is the tile's whole contraction (no split-K, no row groups).
+// One statement for l4p_gemm and l4p_gemm_group: gemm_body honours kw_cols unconditionally.
+static bool kw_cols_ok(int mode, const GemmParams& p) {
+    if (mode != 0 || p.w_gr > 0 || p.splitk > 1 || p.relu_in || p.kw_cols % 128 || p.kw_len < 1 || p.K % 8) {
+        l4p_set_error("l4p_gemm: kw_cols needs a dense GEMM without split-K / row groups, kw_cols a multiple of 128");
+        return false;
+    }
+    return true;
+}
 #ifdef GEMM_HAS_8P
 // A handful of rows (gemm_skinny.hpp: one wave per 16 x 32 output block, operands streamed into fragment registers; bit-identical to
 // the LDS-staged kernels).  The wave count bounds it to problems whose weight stream is re-read by few row blocks.
@@ -261,6 +271,8 @@ static bool gemm_is_small_deep(const GemmParams& p) {
     return !big && p.splitk <= 1 && !p.relu_in && t64 <= 256 && p.K >= 6 * 64 && !(p.tuning & 1) && p.w_gr == 0;
 }
 int GEMM_GROUP_FN(const GemmParams* p, int n, hipStream_t stream) {
+    for (int i = 0; i < n; ++i)  // (before anything is launched: a refused member leaves every output untouched)
+        if (p[i].kw_cols > 0 && !kw_cols_ok(0, p[i])) return L4P_E_INVALID;
     const int deep = knob(KNOB_GEMM_DEEP);
     const int group = knob(KNOB_GEMM_GROUP);
     if (group && n >= 2 && n <= L4P_GEMM_GROUP_MAX) {  // all of them skinny: one launch of the one-wave kernel
@@ -368,10 +380,7 @@ static int launch_subpixel(const GemmParams& p, hipStream_t stream) {
 static int GEMM_FN_impl(int mode, const GemmParams& p, hipStream_t stream) {
     if (mode == 2) return launch_subpixel(p, stream);
     if (p.kw_cols > 0) {  // block-structured weights (l4p_gemm_desc.kw_cols): the LDS-staged kernels, whose k-tile range is per tile
-        if (mode != 0 || p.w_gr > 0 || p.splitk > 1 || p.relu_in || p.kw_cols % 128 || p.kw_len < 1 || p.K % 8) {
-            l4p_set_error("l4p_gemm: kw_cols needs a dense GEMM without split-K / row groups, kw_cols a multiple of 128");
-            return L4P_E_INVALID;
-        }
+        if (!kw_cols_ok(mode, p)) return L4P_E_INVALID;
         const long long t64 = (long long)((p.M + 127) / 128) * ((p.N + 63) / 64);
         if constexpr (sizeof(GEMM_T) == 2) {
             if (t64 <= 256) return launch_cfg<128, 64, 0, true, 4>(p, stream);
