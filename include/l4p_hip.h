@@ -43,7 +43,8 @@ typedef void* l4p_stream; /* hipStream_t */
 typedef struct l4p_engine l4p_engine;
 
 const char* l4p_last_error(void);
-int l4p_abi_version(void); /* 17: evaluation metrics (l4p_metric_ws_bytes, l4p_metric_depth, l4p_metric_flow, l4p_metric_mask,
+int l4p_abi_version(void); /* 18: the L4PDataset base class (l4p_gt_dense_clip, l4p_gt_query_select, l4p_gt_tracks_clip);
+                              * 17: evaluation metrics (l4p_metric_ws_bytes, l4p_metric_depth, l4p_metric_flow, l4p_metric_mask,
                               * l4p_metric_tracks, l4p_metric_cameras, l4p_select_median_dev);
                               * 16: the free-viewpoint 4D renderer (l4p_view_splat, l4p_view_mesh, l4p_view_resolve);
                               * 15: l4p_conv3d_subpixel, knob dpt_fold_rn (dpt.<task>.fold{i}.w / .b);
@@ -881,6 +882,73 @@ int l4p_instance_mask_clip(l4p_stream stream, const unsigned char* src, int n_sr
  * the image ignored, kornia's default border) is > 0 there.  sel (device int[M]) receives the kept m in ascending
  * order, *count (device int) their number; when none is kept, sel = 0..M-1 and *count = M (:462-463). */
 int l4p_seg_query_select(l4p_stream stream, const float* mask, int h, int w, const int* cells, int M, int* sel, int* count);
+
+/* ------------------------------------------------------------------------------------------------
+ * L4PDataset base class: ground-truth clips (l4p/data/l4p_dataset_mini.py:126-395, 499-519, 576-580).  Raw float32
+ * tensors of one sample in HBM -> the sample dict's tensors, three launches (csrc/gt_prep.hip).  The file is built
+ * without floating-point contraction: every operation named below rounds on its own, as the reference's separate
+ * torch operations do.
+ * ------------------------------------------------------------------------------------------------ */
+
+#define L4P_GT_MAX_FIELDS 10
+#define L4P_GT_NEAREST 0
+#define L4P_GT_BILINEAR 1
+
+/* One dense field of a sample (rgb_b3thw, depth_b1thw, the flows, the masks and their valid masks). */
+typedef struct l4p_gt_field {
+    const float* src;      /* device [channels][T0][H][W] */
+    const float* src_swap; /* flow fields: the opposite direction's tensor (same layout), read where the frame table's
+                            * swap flag is 1 (mirror_and_pad, :132-162); NULL for every other field (the flag is ignored) */
+    float* out;            /* device [channels][Tn][Hn][Wn] */
+    int channels;          /* 1..3 */
+    int mode;              /* L4P_GT_NEAREST: F.interpolate(mode="nearest"), :266; L4P_GT_BILINEAR: mode="trilinear" with
+                            * the frame count unchanged = bilinear per frame, w0 * v0 + w1 * v1 per axis (ATen's order), then
+                            * 1 * v + 0 * v for the time axis (ATen copies an axis of unchanged size with weights (1, 0) on one
+                            * index: finite values pass, inf becomes nan) */
+    int apply_scale;       /* 1: multiply channel c by scale[c] after the interpolation (:267-269, flow u by
+                            * float32(res_w / W), flow v by float32(res_h / H)) */
+    int normalize;         /* 1: then (x - mean[c]) / stdv[c], IEEE subtract and divide (:576-580, rgb) */
+    float scale[3];
+    float mean[3];
+    float stdv[3];
+} l4p_gt_field;
+
+/* Every dense field of one sample in one launch, parallel over (field, channel, frame) x pixel tiles.  fields: HOST
+ * array, copied into the kernel arguments at call time.  All sources are [channels][T0][H][W].
+ * frame_table: device int[Tn][2] = (source frame, swap flag) of every output frame: mirror_and_pad (:126-190)
+ * iterated as :558-560 iterates it, or repeat_single_frame (:192-235), with the temporal crop (:337) applied; the
+ * swap flag is the flow-direction parity of the mirror rounds.
+ * ynear / xnear: device int[Hn] / int[Wn], l4p_torch_nearest_table with the crop offset folded in (identity + offset
+ * when the reference skips the resize, :247-248).  yi0, yi1, ylam / xi0, xi1, xlam: device tables of
+ * l4p_resize_index_table for the bilinear fields (for an axis of unchanged size the caller passes i1 = i0, lambda = 0, ATen's
+ * rule for such an axis); may be NULL when no field is bilinear.
+ * A frame or table entry outside the source writes NaN, never reads out of range. */
+int l4p_gt_dense_clip(l4p_stream stream, const l4p_gt_field* fields, int n_fields, int T0, int H, int W,
+                      const int* frame_table, const int* ynear, const int* xnear, const int* yi0, const int* yi1,
+                      const float* ylam, const int* xi0, const int* xi1, const float* xlam, int Tn, int Hn, int Wn);
+
+/* The bounds filter of crop (:356-365): query n of queries (device float [N][3] = t, x, y) is kept iff
+ * t0 < q_t < t0 + Tn, j0 < q_x < j0 + Wn and i0 < q_y < i0 + Hn (strict float32 compares against the integer bounds).
+ * sel (device int[N]) receives the kept n in ascending order, *count (device int) their number - the 4 bytes the
+ * host reads back.  One workgroup.  scale_queries = 1 (this engine's scale_queries_on_resize extension): q_x and q_y are
+ * first multiplied by fw = float32(res_w / W) and fh = float32(res_h / H). */
+int l4p_gt_query_select(l4p_stream stream, const float* queries, int N, int t0, int Tn, int i0, int Hn, int j0, int Wn,
+                        int scale_queries, float fw, float fh, int* sel, int* count);
+
+/* The track tensors of the M kept rows (sel: device int[M], NULL = rows 0..M-1; frame_table as above, no swap):
+ *   gather through sel and the frame table (:175-186, :347, :365-374);
+ *   scale_traj = 1: x *= fw, y *= fh (:270-272);
+ *   cropped = 1 (0: the crop was a no-op and the reference returned at :308-309): x -= j0, y -= i0 (:377-379);
+ *     vis cleared where x >= Wn, x < 0, y >= Hn or y < 0 (:381-384); queries -= (t0, j0, i0) (:390-393);
+ *   causal = 1: valid &= (t + 0.5 >= q_t), causal = -1: valid &= (t + 0.5 <= q_t), 0: unchanged (:499-519).
+ * traj [N][2][T0] -> traj_out [M][2][Tn]; vis / valid: uint8 [N][T0] -> [M][Tn] (bool tensors cross as uint8);
+ * depth [N][T0] -> depth_out [M][Tn], both NULL when the sample has no track depth; queries [N][3] -> queries_out
+ * [M][3]; labels [N] -> labels_out [M].  M == 0 launches nothing. */
+int l4p_gt_tracks_clip(l4p_stream stream, const float* traj, const unsigned char* vis, const unsigned char* valid,
+                       const float* depth, const float* queries, const float* labels, int N, int T0, const int* sel, int M,
+                       const int* frame_table, int Tn, int scale_traj, int scale_queries, float fw, float fh, int cropped,
+                       int t0, int i0, int j0, int Hn, int Wn, int causal, float* traj_out, unsigned char* vis_out,
+                       unsigned char* valid_out, float* depth_out, float* queries_out, float* labels_out);
 
 #ifdef __cplusplus
 }

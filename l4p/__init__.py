@@ -3,7 +3,8 @@
 The reference's callers import the model and data surface under the package name ``l4p``
 (/root/reference/demo/demo.py:12-17: ``from l4p.models.utils import prepare_model``,
 ``from l4p.data.video_dataset import VideoDataset``, ``from l4p.data.davis import DavisDataset``,
-``from l4p.data.dycheck_dataset import DycheckDataset``; configs/model.yaml names ``l4p.l4p.L4PLitModule``,
+``from l4p.data.dycheck_dataset import DycheckDataset``; every reference dataset starts with
+``from l4p.data.l4p_dataset_mini import L4PDataset, L4PData``; configs/model.yaml names ``l4p.l4p.L4PLitModule``,
 ``l4p.models.l4p_videomae.L4P_VideoMAE``, ``l4p.models.task_heads.…``).  With this directory ahead of the reference on
 ``sys.path`` those lines resolve to the engine unchanged: ``l4p.<x>`` IS the module ``l4p_amd.<x>`` (the same module
 object, no copy, no reference code).  Sub-modules the engine does not provide (the reference's own visualisation module and viewer, the
@@ -32,7 +33,7 @@ class _AliasFinder(importlib.abc.MetaPathFinder, importlib.abc.Loader):
             raise ModuleNotFoundError(
                 f"No module named {fullname!r}: the MI355X engine (package l4p_amd, aliased as l4p) does not provide it — it "
                 "covers the inference hot path and the demo's datasets (l4p.l4p, l4p.metrics, l4p.models.*, l4p.data.video_dataset, l4p.data.davis, "
-                "l4p.data.dycheck_dataset, l4p.utils.geometry_utils, l4p.utils.recon4d, l4p.utils.vis2d, l4p.utils.view4d)",
+                "l4p.data.dycheck_dataset, l4p.data.l4p_dataset_mini, l4p.data.npz_dataset, l4p.utils.geometry_utils, l4p.utils.recon4d, l4p.utils.vis2d, l4p.utils.view4d)",
                 name=fullname)
         return importlib.util.spec_from_loader(fullname, self, is_package=found.submodule_search_locations is not None)
 

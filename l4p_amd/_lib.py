@@ -14,7 +14,7 @@ L4P_BF16 = 0
 L4P_F32 = 1
 L4P_F16 = 2  # IEEE half storage / f16 MFMA: the arithmetic class of the reference's "16-mixed" (fp16 autocast)
 
-ABI_VERSION = 17  # what l4p_abi_version() of the library this binding was written against returns (include/l4p_hip.h)
+ABI_VERSION = 18  # what l4p_abi_version() of the library this binding was written against returns (include/l4p_hip.h)
 
 EPI_DENSE, EPI_QKV, EPI_CONVT, EPI_MASKDOT = 0, 1, 2, 3
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
@@ -83,6 +83,20 @@ class TrackCfg(C.Structure):
 
     _fields_ = [(n, C.c_int) for n in ("dim", "tokens", "nt", "nh", "nw", "sam_depth", "sam_heads", "sam_mlp", "out_dim_factor",
                                         "T", "H", "W")]
+
+
+GT_MAX_FIELDS = 10
+GT_NEAREST, GT_BILINEAR = 0, 1
+
+
+class GtField(C.Structure):
+    """Mirror of ``l4p_gt_field``."""
+
+    _fields_ = [
+        ("src", C.c_void_p), ("src_swap", C.c_void_p), ("out", C.c_void_p),
+        ("channels", C.c_int), ("mode", C.c_int), ("apply_scale", C.c_int), ("normalize", C.c_int),
+        ("scale", C.c_float * 3), ("mean", C.c_float * 3), ("stdv", C.c_float * 3),
+    ]
 
 
 # name -> (restype, argtypes); every symbol include/l4p_hip.h declares must appear here
@@ -169,6 +183,9 @@ SIGNATURES = {
     "l4p_torch_nearest_table": (_I, [_I, _I, _VP]),
     "l4p_instance_mask_clip": (_I, [_VP, _VP, _I, _I, _I, _I, _VP, _VP, _VP, _VP, _I, _I, _I]),
     "l4p_seg_query_select": (_I, [_VP, _VP, _I, _I, _VP, _I, _VP, _VP]),
+    "l4p_gt_dense_clip": (_I, [_VP, C.POINTER(GtField), _I, _I, _I, _I] + [_VP] * 9 + [_I] * 3),
+    "l4p_gt_query_select": (_I, [_VP, _VP] + [_I] * 8 + [_F, _F, _VP, _VP]),
+    "l4p_gt_tracks_clip": (_I, [_VP] * 7 + [_I, _I, _VP, _I, _VP] + [_I] * 3 + [_F, _F] + [_I] * 7 + [_VP] * 6),
     "l4p_track_readout": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I]),
     "l4p_track_prepare": (_I, [_VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _I]),
     "l4p_track_commit": (_I, [_VP] * 9 + [_I] * 5 + [_VP] * 5 + [_I, _I]),

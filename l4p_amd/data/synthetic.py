@@ -100,3 +100,52 @@ def write_dycheck_tree(root: str, seq: str, frames, calibration) -> str:
     with open(os.path.join(root, seq, "calibration.txt"), "w") as fh:
         fh.write(" ".join(repr(float(v)) for v in calibration) + "\n")
     return root
+
+
+def synthetic_ground_truth(seed: int, T: int, H: int, W: int, N: int):
+    """A raw ground-truth clip as a dataset decodes it, under the L4PData field names (numpy, no batch dimension): rgb in [0, 1];
+    depth with some inf, nan and 0 entries and its valid mask; both flow directions and their valid masks; a blob motion mask, its
+    valid mask and an instance mask; N tracks (some leave the image) with visibility, validity and depth; one query per track placed
+    on the track at a frame centre; point labels; intrinsics, extrinsics and relative poses."""
+    import numpy as np
+
+    rng = np.random.default_rng(seed)
+    f32 = np.float32
+    out = {"rgb_b3thw": np.ascontiguousarray(synthetic_video(seed, T, H, W).transpose(3, 0, 1, 2)).astype(f32) / f32(255)}
+    t = np.arange(T)[:, None, None]
+    y = np.arange(H)[None, :, None]
+    x = np.arange(W)[None, None, :]
+    depth = (2.0 + 0.5 * np.sin(0.4 * x + 0.3 * t) + 0.1 * y + rng.uniform(0, 0.2, size=(T, H, W))).astype(f32)
+    kind = rng.integers(0, 12, size=(T, H, W))
+    depth[kind == 0] = np.inf
+    depth[kind == 1] = np.nan
+    depth[kind == 2] = 0
+    out["depth_b1thw"] = depth[None]
+    out["depth_valid_b1thw"] = (np.isfinite(depth) & (depth > 0)).astype(f32)[None]
+    for name in ("backward", "forward"):
+        out[f"flow_2d_{name}_b2thw"] = rng.normal(0, 1.5, size=(2, T, H, W)).astype(f32)
+        out[f"flow_2d_{name}_valid_b2thw"] = np.repeat((rng.uniform(size=(1, T, H, W)) > 0.2).astype(f32), 2, axis=0)
+    blob = synthetic_masks(seed + 1, T, H, W, "blob")
+    out["dyn_mask_b1thw"] = (blob == 1).astype(f32)[None]
+    out["dyn_mask_valid_b1thw"] = (rng.uniform(size=(1, T, H, W)) > 0.1).astype(f32)
+    out["instanceseg_b1thw"] = (blob > 0).astype(f32)[None]
+    # tracks: a random walk from a start inside (or just outside) the image
+    start = np.stack([rng.uniform(-1.5, W + 1.5, size=N), rng.uniform(-1.5, H + 1.5, size=N)], axis=1)
+    traj = (start[:, :, None] + np.cumsum(rng.normal(0, 0.8, size=(N, 2, T)), axis=2)).astype(f32)
+    out["track_2d_traj_bn2t"] = traj
+    out["track_2d_vis_bn1t"] = rng.uniform(size=(N, 1, T)) > 0.25
+    out["track_2d_valid_bn1t"] = rng.uniform(size=(N, 1, T)) > 0.15
+    out["track_2d_depth_bn1t"] = rng.uniform(1, 5, size=(N, 1, T)).astype(f32)
+    qt = rng.integers(0, T, size=N)
+    n = np.arange(N)
+    out["track_2d_pointquerries_bn3"] = np.stack([qt.astype(f32) + f32(0.5), traj[n, 0, qt], traj[n, 1, qt]], axis=1).astype(f32)
+    out["track_2d_pointlabels_bn"] = np.ones(N, dtype=f32)
+    K = np.eye(4, dtype=f32)
+    K[0, 0], K[1, 1], K[0, 2], K[1, 2] = 1.1 * W, 1.3 * W, W / 2 - 0.25, H / 2 + 0.75
+    out["intrinsics_b44t"] = np.repeat(K[:, :, None], T, axis=2) + (0.01 * np.arange(T, dtype=f32))[None, None, :] * (K > 1)[:, :, None]
+    E = np.repeat(np.eye(4, dtype=f32)[:, :, None], T, axis=2)
+    E[:3, 3, :] = rng.normal(0, 0.3, size=(3, T)).astype(f32)
+    out["extrinsics_b44t"] = E
+    out["rel_pose_b6t"] = rng.normal(0, 0.2, size=(6, T)).astype(f32)
+    out["intrinsics_b44t"] = out["intrinsics_b44t"].astype(f32)
+    return out

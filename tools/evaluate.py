@@ -9,6 +9,13 @@ Prints one JSON line per clip (the scalars of that clip) and one with the mean o
 
   python tools/evaluate.py CLIPS_DIR --ckpt model.ckpt [--precision 16-mixed] [--depth-align median|none|lstsq]
   python tools/evaluate.py CLIPS_DIR --synthetic [--mini]      # seeded weights, as demo/demo.py --synthetic: plumbing, not numbers
+
+With --raw the .npz files hold RAW clips instead (the dataset's own resolution and length, rgb as float in [0, 1] or uint8): they
+go through l4p_amd.data.NpzClipDataset - resize, crop, mirror padding and query filtering on the GPU - and a
+DataLoader(batch_size=1) into test_step.  With --raw --synthetic and an empty or missing CLIPS_DIR, two seeded raw clips
+(l4p_amd.data.synthetic.synthetic_ground_truth) are written there first.
+
+  python tools/evaluate.py RAW_DIR --raw --resize 224 224 [--crop 16 224 224] [--spacing 0.02] [--seed 0] --ckpt model.ckpt
 """
 import argparse
 import glob
@@ -61,6 +68,26 @@ def mean_over_clips(rows) -> dict:
     return out
 
 
+def raw_loader(clips: str, resize, crop, spacing: float, seed: int):
+    """DataLoader(batch_size=1) over NpzClipDataset(clips): centre crop from the first frame; clips with their own queries keep
+    them (scaled with the resize), the others get the uniform grid of ``spacing``."""
+    from l4p_amd.data import NpzClipDataset
+
+    torch.manual_seed(seed)
+    ds = NpzClipDataset(clips, crop_size=tuple(crop) if crop else None, resize_size=tuple(resize) if resize else None, center_crop=True,
+                        start_crop_time=True, estimation_directions=[1], track_2d_querry_sampling_version="uniform",
+                        track_2d_querry_sampling_spacing=spacing, scale_queries_on_resize=True)
+    return torch.utils.data.DataLoader(ds, batch_size=1, shuffle=False, num_workers=0)
+
+
+def write_synthetic_raw(clips: str, n: int = 2, T: int = 9, H: int = 56, W: int = 64, N: int = 8):
+    os.makedirs(clips, exist_ok=True)
+    from l4p_amd.data.synthetic import synthetic_ground_truth
+
+    for i in range(n):
+        np.savez(os.path.join(clips, f"synthetic_{i}.npz"), **synthetic_ground_truth(40 + i, T, H, W, N))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("clips", help="directory of .npz clips")
@@ -71,9 +98,17 @@ def main():
     ap.add_argument("--max-queries", type=int, default=128)
     ap.add_argument("--precision", default="16-mixed")
     ap.add_argument("--depth-align", default="median", choices=["median", "none", "lstsq"])
+    ap.add_argument("--raw", action="store_true", help="the .npz files are raw clips: prepare them with NpzClipDataset on the GPU")
+    ap.add_argument("--resize", type=int, nargs=2, default=None, metavar=("H", "W"), help="with --raw: resize_size")
+    ap.add_argument("--crop", type=int, nargs=3, default=None, metavar=("T", "H", "W"), help="with --raw: crop_size (default: the "
+                    "clip's length rounded up to a multiple of 8, at least 16, x 224 x 224)")
+    ap.add_argument("--spacing", type=float, default=0.02, help="with --raw: grid spacing of the queries of clips without tracks")
+    ap.add_argument("--seed", type=int, default=0, help="with --raw: torch.manual_seed before the clips are drawn")
     args = ap.parse_args()
     if not args.synthetic and not args.ckpt:
         ap.error("--ckpt (or --synthetic)")
+    if args.raw and args.synthetic and not glob.glob(os.path.join(args.clips, "*.npz")):
+        write_synthetic_raw(args.clips)
     files = sorted(glob.glob(os.path.join(args.clips, "*.npz")))
     if not files:
         ap.error(f"no .npz clips under {args.clips}")
@@ -97,10 +132,18 @@ def main():
                               precision=args.precision, accelerator="gpu")
     model.metrics_module = L4PMetrics(depth_align=args.depth_align)
     rows = []
-    for i, f in enumerate(files):
-        with np.load(f, allow_pickle=False) as z:
-            batch = npz_to_batch(z)
-        batch.setdefault("seq_name", [os.path.splitext(os.path.basename(f))[0]])
+
+    def batches():
+        if args.raw:
+            yield from raw_loader(args.clips, args.resize, args.crop, args.spacing, args.seed)
+            return
+        for f in files:
+            with np.load(f, allow_pickle=False) as z:
+                batch = npz_to_batch(z)
+            batch.setdefault("seq_name", [os.path.splitext(os.path.basename(f))[0]])
+            yield batch
+
+    for i, batch in enumerate(batches()):
         with torch.no_grad():
             model.test_step(batch, i)
         row = clip_scalars(model.last_log)
