@@ -109,7 +109,7 @@ int l4p_stream_destroy(l4p_stream stream);
  *   "track_fold_pair" (L4P_TRACK_FOLD_PAIR, default 0): 1 = K' of the folded image -> token scores as a PAIR of bf16 matrices (l4p_split_hilo; measured: changes nothing)
  *   "track_delta_kernel" (L4P_TRACK_DELTA_KERNEL, default 1): delta = P x V' + b_out by its own streaming kernel (l4p_i2t_delta, bit-identical); 0 = the row-grouped GEMM
  * The GEMM launchers (A/B and tuning aids):
- *   "gemm_persist" (L4P_GEMM_PERSIST, default 1): only in a -DGEMM_8P_PERSIST_EXPERIMENT build: 0 = the plain launch of the 8-phase kernel
+ *   "gemm_persist" (L4P_GEMM_PERSIST, default 1): kept so that setting it succeeds; no build launches the persistent form of the 8-phase kernel, so it selects nothing
  *   "skinny_max_m" (L4P_SKINNY_MAX_M, default 128): most rows the one-wave kernel of "gemm_skinny" takes
  *   "gemm_deep"  (L4P_GEMM_DEEP, default 1): small problems (at most one workgroup per CU, K >= 384) on the four-stage 128x64 kernel; 0 = the two-deep ring
  *   "gemm_group" (L4P_GEMM_GROUP, default 1): l4p_gemm_group runs independent projections as one launch; 0 = one launch each

@@ -182,7 +182,7 @@ struct EncWs {
 // fc2 (K = mlp_hidden = 6144: 96 k-tiles in a row) at batch 1 gives each CU one latency-bound chain of k-tiles; two K slices
 // double the workgroups in flight (69 -> ~50 us including the reduction pass).  Not worth it once M fills the chip.
 // With enough k-tiles per slice the slices go to the 8-phase kernel instead: as many slices of the 256x256 tiles as fill the
-// chip about once (batch 1: 48 tiles x 4 = 192 workgroups), the form gemm_launch.inc routes to that kernel.
+// chip about once (batch 1: 48 tiles x 4 = 192 workgroups), the form gemm_select.hpp routes to that kernel.
 static int enc_fc2_splitk(const l4p_engine* e, size_t M) {
     const l4p_encoder_cfg& c = e->enc;
     const size_t tiles = ((M + 127) / 128) * (((size_t)c.dim + 63) / 64);

@@ -33,7 +33,7 @@ int splitk_for(long long M, int N, int K, int es) {  // keep in sync with l4p_am
     const int nk = (K + 128 / es - 1) / (128 / es);
     if (nk < 32) return 1;
     long long s;
-    if (N >= 256) {  // 128x128 tiles, two workgroups per CU: aim at 512 workgroups (gemm_launch.inc picks the tile)
+    if (N >= 256) {  // 128x128 tiles, two workgroups per CU: aim at 512 workgroups (gemm_select.hpp picks the tile)
         const long long tiles = ((M + 127) / 128) * ((N + 127) / 128);
         if (tiles >= 400) return 1;
         s = 512 / tiles;

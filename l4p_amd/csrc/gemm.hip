@@ -1,7 +1,11 @@
 #include "gemm.hpp"
-int launch_gemm_bf16(int mode, const GemmParams& p, hipStream_t stream);
-int launch_gemm_f16(int mode, const GemmParams& p, hipStream_t stream);
-int launch_gemm_f32(int mode, const GemmParams& p, hipStream_t stream);
+
+// the element type's instantiation of the launcher (gemm_launch.hpp)
+static int launch_gemm_of(int dtype, int mode, const GemmParams& p, hipStream_t stream) {
+    return dtype == L4P_BF16 ? launch_gemm_typed<bf16_t>(mode, p, stream)
+           : dtype == L4P_F16 ? launch_gemm_typed<f16_t>(mode, p, stream)
+                              : launch_gemm_typed<float>(mode, p, stream);
+}
 
 // l4p_conv3d_subpixel (mode 2): the arguments the kernels rely on, then the conv descriptor they read (output grid == input grid, stride 1)
 static int launch_subpixel_checked(int dtype, const GemmParams& d, hipStream_t stream) {
@@ -30,7 +34,7 @@ static int launch_subpixel_checked(int dtype, const GemmParams& d, hipStream_t s
     p.st = p.sh = p.sw = 1;
     p.K = (int)p.ldw;
     p.epi = L4P_EPI_CONVT;
-    return dtype == L4P_BF16 ? launch_gemm_bf16(2, p, stream) : dtype == L4P_F16 ? launch_gemm_f16(2, p, stream) : launch_gemm_f32(2, p, stream);
+    return launch_gemm_of(dtype, 2, p, stream);
 }
 
 int launch_gemm(int dtype, int mode, const GemmParams& p, hipStream_t stream) {
@@ -53,11 +57,9 @@ int launch_gemm(int dtype, int mode, const GemmParams& p, hipStream_t stream) {
             return L4P_E_INVALID;
         }
     }
-    return dtype == L4P_BF16 ? launch_gemm_bf16(mode, p, stream) : dtype == L4P_F16 ? launch_gemm_f16(mode, p, stream) : launch_gemm_f32(mode, p, stream);
+    return launch_gemm_of(dtype, mode, p, stream);
 }
 
-int launch_gemm_group_bf16(const GemmParams* p, int n, hipStream_t stream);
-int launch_gemm_group_f16(const GemmParams* p, int n, hipStream_t stream);
 int launch_gemm_group(int dtype, const GemmParams* p, int n, hipStream_t stream) {
     if (!p || n < 1 || n > L4P_GEMM_GROUP_MAX) {
         l4p_set_error("gemm_group: 1 <= n <= %d descriptors", L4P_GEMM_GROUP_MAX);
@@ -69,7 +71,7 @@ int launch_gemm_group(int dtype, const GemmParams* p, int n, hipStream_t stream)
                 p[i].splitk > 1)
                 goto one_by_one;
         }
-        return dtype == L4P_F16 ? launch_gemm_group_f16(p, n, stream) : launch_gemm_group_bf16(p, n, stream);
+        return dtype == L4P_F16 ? launch_gemm_group_typed<f16_t>(p, n, stream) : launch_gemm_group_typed<bf16_t>(p, n, stream);
     }
 one_by_one:
     for (int i = 0; i < n; ++i) {

@@ -934,7 +934,7 @@ __device__ __forceinline__ void gemm_epilogue_subpixel(const GemmParams& p, f32x
 }
 
 // the plain dense family (activation x residual kind); false = a combination that has no lean body.  Host-side twin of the
-// condition: dense_epilogue_is_lean() in gemm_launch.inc.
+// condition: dense_epilogue_is_lean() in gemm_select.hpp.
 template <typename T, int TM, int TN, class RowMap>
 __device__ __forceinline__ bool gemm_epilogue_dense_cases(const GemmParams& p, f32x4 (&acc)[TM][TN], int m_wave0, int n_wave0,
                                                           int li, int kg, const RowMap& crow) {
@@ -1412,3 +1412,8 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm_group_kernel(const GemmGroup
 // host launcher (gemm.hip)
 int launch_gemm(int dtype, int mode, const GemmParams& p, hipStream_t stream);
 int launch_gemm_group(int dtype, const GemmParams* p, int n, hipStream_t stream);
+// ... and its per-element-type halves (gemm_launch.hpp; instantiated in gemm_bf16.hip / gemm_f16.hip / gemm_f32.hip, the grouped one 16-bit only)
+template <typename T>
+int launch_gemm_typed(int mode, const GemmParams& p, hipStream_t stream);
+template <typename T>
+int launch_gemm_group_typed(const GemmParams* p, int n, hipStream_t stream);

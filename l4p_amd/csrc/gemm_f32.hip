@@ -1,3 +1,2 @@
-#define GEMM_T float
-#define GEMM_FN launch_gemm_f32
-#include "gemm_launch.inc"
+#include "gemm_launch.hpp"
+template int launch_gemm_typed<float>(int mode, const GemmParams& p, hipStream_t stream);

@@ -27,7 +27,7 @@ enum Knob {
     // the tracker window (api_trackwin.hip)
     KNOB_TRACK_FOLD_L0, KNOB_TRACK_FOLD_T2I, KNOB_TRACK_FOLD_T2I_V, KNOB_TRACK_KWIN, KNOB_TRACK_LN_CHAIN, KNOB_TRACK_FOLD_I2T,
     KNOB_TRACK_FOLD_PAIR, KNOB_TRACK_DELTA_KERNEL,
-    // the GEMM launchers (gemm_launch.inc)
+    // the GEMM launchers (gemm_select.hpp / gemm_launch.hpp)
     KNOB_GEMM_PERSIST, KNOB_SKINNY_MAX_M, KNOB_GEMM_DEEP, KNOB_GEMM_GROUP, KNOB_EPI_GENERIC, KNOB_GEMM_VARIANT, KNOB_GEMM_T192,
     // attention.hip, dpt_ops.hip, api.hip
     KNOB_ATTN_PERSIST, KNOB_ATTN_VARIANT, KNOB_UPS_IPT, KNOB_UPS_NT, KNOB_FC2_SPLITK8, KNOB_ENC_DEFER_RES, KNOB_ENC_SK_IN_LN,

@@ -2,7 +2,7 @@
 the GPU cases and the proof that their inputs discriminate cannot drift apart.
 
 A Case is one launch of l4p_gemm / l4p_conv3d_k3: shape, engine type, epilogue, knobs and the kernel form its profiler tag must name
-(csrc/gemm_launch.inc).  Everything here runs on the CPU:
+(csrc/gemm_select.hpp names it, csrc/gemm_launch.hpp launches it).  Everything here runs on the CPU:
 
   * operands: random, rounded to the engine type; the LAST k-chunk (8 elements, 4 for f32: one 16-byte staging chunk) of the left
     operand is multiplied by 4, so a kernel that loses the contraction's tail is far outside the bounds;
@@ -65,6 +65,50 @@ class Case:
     @property
     def chunk(self):
         return 4 if self.mode == L4P_F32 else 8
+
+
+PAD = 8  # columns behind every row of A, W, the outputs and the residuals (the LDS-halo conv requires ldc == N: none there)
+POINTERS = ("A", "W", "bias", "res1", "res2", "out_f32", "out_T", "out_relu_T", "partial", "vt", "k_tiled")
+
+
+def desc_fields(case):
+    """{field of l4p_gemm_desc: value} of the launch a case is: every integer field that is not zero, and 1 for every pointer in
+    POINTERS that is set.  tests/test_gemm_forms_gpu.py fills its descriptors from this (and puts its buffers behind the pointers);
+    tests/test_gemm_select_cpu.py feeds the same values to csrc/gemm_select.hpp on the host."""
+    pad = 0 if case.form.startswith("halo") else PAD
+    f = dict(A=1, W=1, bias=1, M=case.M, N=case.N, K=case.K, act=case.act, epi=case.epi)
+    if case.conv:
+        B, T, H, W, Cin, st, sh, sw, relu_in = case.conv
+        To, Ho, Wo = conv_out_dims(case.conv)
+        f.update(Ti=T, Hi=H, Wi=W, Cin=Cin, To=To, Ho=Ho, Wo=Wo, st=st, sh=sh, sw=sw, relu_in=relu_in, ldw=case.K)
+    else:
+        f.update(lda=case.K + PAD, ldw=case.K + PAD)
+    if case.epi == 1:    # QKV: q dense behind out_T, K and V scattered
+        B, S, H, Dh = case.geo
+        f.update(out_T=1, ldc=H * ops.DP + PAD, k_tiled=1, vt=1, S=S, H=H, Dp=ops.DP)
+        return f
+    if case.epi == 2:    # ConvTranspose: pixel-shuffle scatter behind out_T
+        B, T, H, W, kt, kh, kw, cout = case.geo
+        f.update(out_T=1, Ti=T, Hi=H, Wi=W, kt=kt, kh=kh, kw=kw, Cout=cout)
+        return f
+    if case.rowmap:
+        gr, gs, go = case.rowmap
+        f.update(a_gr=gr, a_gs=gs, a_go=go, c_gr=gr, c_gs=gs, c_go=go)
+    if case.wgr:
+        f.update(w_gr=case.wgr, w_gs=case.N * (case.K + PAD), b_gs=case.N)
+    f["ldc"] = case.N + pad
+    for name in case.outs:
+        f[{"T": "out_T", "f32": "out_f32", "relu": "out_relu_T"}[name]] = 1
+    if case.res and case.inplace:    # the output of the residual's type IS res1
+        if ("f32" if case.res == "f32" else "T") in case.outs:
+            f.update(res1=1, res_f32=int(case.res == "f32"), ldr=case.N + pad)
+    elif case.res:
+        f.update(res1=1, res_f32=int(case.res == "f32"), ldr=case.N + pad, res_mod=case.res_mod)
+        if case.res2:
+            f["res2"] = 1
+    if case.splitk > 1:
+        f.update(splitk=case.splitk, partial=1)
+    return f
 
 
 def phys_rows(case):
@@ -221,7 +265,7 @@ def _forms(form, shapes, modes, **kw):
     return [Case(form, M, N, K, mode, outs=_both(mode), **kw) for (M, N, K) in shapes for mode in modes]
 
 
-# ---- dense forms at their smallest ragged shapes (thresholds: GEMM_FN_impl at the default knobs) ----
+# ---- dense forms at their smallest ragged shapes (thresholds: gemm_select at the default knobs) ----
 STAGED_2 = _forms("sk1 t128x64", [(200, 72, 200), (129, 8, 72)], M16)             # K < 384; one 8-column group; one row past a tile
 STAGED_DEEP = _forms("sk1 t128x64 deep", [(130, 72, 392), (300, 200, 1224)], M16)  # 6.125 and 19.125 k-tiles on the 4-slot ring
 STAGED_WIDE = _forms("sk1 t128x128", [(2500, 2504, 72)], M16 + (L4P_F32,), cls="gemm")  # 20 x 20 = 400 tiles, 100 of 256 x 256
@@ -292,7 +336,7 @@ SWEEP_OUTS = (("T",), ("f32",), ("T", "f32"), ("T", "relu"))
 
 
 def epilogue_is_lean(case):
-    """What the host twins dense_epilogue_is_lean / epilogue_is_lean_8p (csrc/gemm_launch.inc) must return for a dense-epilogue case,
+    """What the host twins dense_epilogue_is_lean / epilogue_is_lean_8p (csrc/gemm_select.hpp) must return for a dense-epilogue case,
     stated from the comments of csrc/gemm.hpp ("Lean epilogue for the plain dense family (L4P_EPI_DENSE, no row maps, no broadcast
     residual)", gemm_epilogue_dense_cases): activation x residual kind is one of (any, none), (none, float), (none, T), (ReLU, T), and
     a second residual exists only beside a T one.  The outputs do not enter."""

@@ -42,7 +42,7 @@ KNOBS_SHIPPED = {"enc_defer_res": 1, "enc_sk_in_ln": 1, "fc2_splitk8": -1}
 #   norm1 of block l + 1 is a "res" launch when block l's MLP sum was handed over (delta at batch 2, partials at batch 1), which
 #   needs block l + 1 not tapped and block l not the last one run.
 # fc2_splitk8 = 8: 48 tiles x 8 slices = 384 workgroups is more than the one round (<= 256) the 8-phase split-K form takes
-# (gemm_launch.inc), so the 8 slices run on the LDS-staged kernel - tagged "sk8", not "8p sk8".
+# (gemm_select.hpp), so the 8 slices run on the LDS-staged kernel - tagged "sk8", not "8p sk8".
 CASES = {
     "default":     dict(clips="a", taps=(0, 3), knobs={}, fc2=(3, " sk4 ", True), res=5),
     "finish":      dict(clips="a", taps=(0, 3), knobs={"enc_sk_in_ln": 0}, fc2=(3, " sk4 ", True), res=3),

@@ -1,7 +1,7 @@
 """Direct parity of the 8-phase 256x256 bf16 kernel (csrc/gemm8p.hpp) — the kernel that carries the batch-4 encoder
 linears, the tracker's tall GEMMs and the N = 256 DPT convs of the benchmarked workload — against plain PyTorch fp32 on
 the same bf16-rounded inputs, at the SHAPES THE BENCH RUNS.  tests/test_kernels_gpu.py's shapes all fall on the 128x128
-kernel (the 8-phase kernel is selected for >= 192..256 tiles of 256x256, gemm_launch.inc), so every test here asserts
+kernel (the 8-phase kernel is selected for >= 192..256 tiles of 256x256, gemm_select.hpp), so every test here asserts
 through the event profiler's tag (l4p_prof_detail) that the launch really was the 8-phase kernel.
 
 Tolerances are tests/test_kernels_gpu.py's: float outputs 1e-3 * max|ref|; bf16 outputs rel-L2 <= 3e-3 and max error
@@ -127,7 +127,7 @@ def test_gemm8p_splitk_f32_residual_inplace(dev, M, N, K, sk):
     tags = [ln[1] for ln in p.lines if ln[0] == "gemm"]
     assert tags and all(f" 8p sk{sk} " in t for t in tags), tags
     if (M, N, K, sk) == (2048, 1408, 6144, 4):
-        assert all("t256x192" in t for t in tags), tags  # (gemm_launch.inc: the split-K form of the 4 x 6 wave tile)
+        assert all("t256x192" in t for t in tags), tags  # (gemm_select.hpp: the split-K form of the 4 x 6 wave tile)
     check(x, a_ref @ w_ref.t() + bias + res, MODE, False)
     # run-to-run bit-reproducible (fixed summation order of the slices)
     x2 = res.clone().cuda()

@@ -1,5 +1,5 @@
-"""Every kernel form the GEMM / conv launcher can pick (csrc/gemm_launch.inc: GEMM_FN_impl, GEMM_GROUP_FN, launch_cfg, launch_8p,
-launch_halo), each at the smallest ragged shape that reaches it, against a float64 reference computed from the same rounded operands
+"""Every kernel form the GEMM / conv launcher can pick (csrc/gemm_select.hpp: gemm_select, gemm_group_select; csrc/gemm_launch.hpp:
+launch_cfg, launch_8p, launch_halo), each at the smallest ragged shape that reaches it, against a float64 reference computed from the same rounded operands
 (tests/gemm_forms_cases.py holds the cases and their CPU side; reference call sites: include/l4p_hip.h, l4p_gemm_desc).  Every case
 asserts through the event profiler (l4p_prof_detail) that there was exactly one launch and that its tag names the form the case is
 about, so a moved threshold in the launcher fails here instead of silently leaving a form untested.
@@ -32,7 +32,7 @@ from tests.test_gemm8p_gpu import prof_tags
 from tests.test_kernels_gpu import check
 
 E_INVALID = -1  # L4P_E_INVALID
-PAD, GUARD_ROWS = 8, 16
+PAD, GUARD_ROWS = G.PAD, 16
 SENTINEL = -24576.0  # (exact in bf16 and f16; the data are of order 1 to 10)
 CLASSES = ("gemm", "gemm_small", "conv3d")
 NAN = float("nan")
@@ -60,6 +60,16 @@ def launches(p):
     return [(ln[0], ln[1], int(ln[2])) for ln in p.lines if ln[0] in CLASSES]
 
 
+def _desc_ints(case):
+    """a descriptor with every integer field of the case (tests/gemm_forms_cases.py desc_fields: the values that
+    tests/test_gemm_select_cpu.py pushes through the launcher's selection on the host); the caller puts its buffers behind the pointers"""
+    d = GemmDesc()
+    for name, value in G.desc_fields(case).items():
+        if name not in G.POINTERS:
+            setattr(d, name, value)
+    return d
+
+
 class Run:
     """One case on the device: builds the descriptor with guarded outputs, launches, asserts the profiler tag and the guards."""
 
@@ -69,40 +79,26 @@ class Run:
             knob(name, value)
         td = ops.torch_dtype(case.mode)
         a, w, bias = G.operands(case)
-        d = self.d = GemmDesc()
-        halo = case.form.startswith("halo")
-        pad = 0 if halo else PAD
+        assert case.epi == EPI_DENSE
+        d, fields = _desc_ints(case), G.desc_fields(case)
+        self.d = d
+        pad = fields["ldc"] - case.N  # (0 for the LDS-halo conv)
         self.keep = []
         if case.conv:
-            B, T, H, W, Cin, st, sh, sw, relu_in = case.conv
-            To, Ho, Wo = G.conv_out_dims(case.conv)
             A = a.cuda()
-            d.A = A.data_ptr()
-            d.Ti, d.Hi, d.Wi, d.Cin, d.To, d.Ho, d.Wo = T, H, W, Cin, To, Ho, Wo
-            d.st, d.sh, d.sw, d.relu_in = st, sh, sw, relu_in
             Wd = torch.zeros(((case.N + 255) // 256 * 256, case.K), dtype=td)
             Wd[:case.N] = w
             Wd = Wd.cuda()
-            d.ldw = case.K
         else:
             A = _padded(a, 100.0)
-            d.A, d.lda = A.data_ptr(), case.K + PAD
             # (plain weights: whole tiles are read, rows >= N zero; a group's matrix has exactly N rows, the next group's behind it)
             Wd = _padded(w, 100.0, rows=(w.shape[0] + 255) // 256 * 256 + (256 if case.wgr else 0))
-            d.ldw = case.K + PAD
-        d.W = Wd.data_ptr()
         bd = bias.cuda()
-        d.M, d.N, d.K, d.bias, d.act, d.epi = case.M, case.N, case.K, bd.data_ptr(), case.act, EPI_DENSE
+        d.A, d.W, d.bias = A.data_ptr(), Wd.data_ptr(), bd.data_ptr()
         self.keep += [A, Wd, bd]
-        if case.rowmap:
-            d.a_gr, d.a_gs, d.a_go = case.rowmap
-            d.c_gr, d.c_gs, d.c_go = case.rowmap
-        if case.wgr:
-            d.w_gr, d.w_gs, d.b_gs = case.wgr, case.N * (case.K + PAD), case.N
         rows = case.rows_phys
         self.inside = torch.zeros((rows + GUARD_ROWS, case.N + pad), dtype=torch.bool, device="cuda")
         self.inside[G.phys_rows(case).cuda(), :case.N] = True
-        d.ldc = case.N + pad
         r1, r2 = G.residuals(case)
         self.bufs = {}
         for name in case.outs:
@@ -111,19 +107,20 @@ class Run:
             buf = torch.full((rows + GUARD_ROWS, case.N + pad), SENTINEL if alias else NAN, dtype=dt, device="cuda")
             if alias:
                 buf[:rows, :case.N] = r1.cuda()
-                d.res1, d.res_f32, d.ldr = buf.data_ptr(), int(case.res == "f32"), case.N + pad
+                d.res1 = buf.data_ptr()
             setattr(d, {"T": "out_T", "f32": "out_f32", "relu": "out_relu_T"}[name], buf.data_ptr())
             self.bufs[name] = buf
         if r1 is not None and not case.inplace:
             rd = [(_padded(r, 100.0) if pad else r.cuda()) for r in (r1, r2) if r is not None]
-            d.res1, d.res_f32, d.ldr, d.res_mod = rd[0].data_ptr(), int(case.res == "f32"), case.N + pad, case.res_mod
+            d.res1 = rd[0].data_ptr()
             if r2 is not None:
                 d.res2 = rd[1].data_ptr()
             self.keep += rd
         self.partial = None
         if case.splitk > 1:
             self.partial = torch.full((case.splitk * case.M * case.N + GUARD_ROWS * case.N,), NAN, dtype=torch.float32, device="cuda")
-            d.splitk, d.partial = case.splitk, self.partial.data_ptr()
+            d.partial = self.partial.data_ptr()
+        assert all(bool(getattr(d, name)) == bool(fields.get(name)) for name in G.POINTERS), "desc_fields and the buffers disagree"
         self.before = {name: buf.clone() for name, buf in self.bufs.items()}
 
     def launch(self):
@@ -184,7 +181,7 @@ def test_dense_form(dev, knob, case):
 
 @cases(G.STAGED_DEEP)
 def test_deep_ring_equals_two_stages_bitwise(dev, knob, case):
-    """Four stages against two (knob gemm_deep = 0): the same sums in the same order (GEMM_FN_impl), so bit-identical outputs."""
+    """Four stages against two (knob gemm_deep = 0): the same sums in the same order (gemm_select), so bit-identical outputs."""
     deep = run_and_compare(case, knob)
     plain = run_and_compare(dataclasses.replace(case, form="sk1 t128x64", knobs=(("gemm_deep", 0),)), knob)
     for name in case.outs:
@@ -244,11 +241,11 @@ def test_qkv_epilogue_on_the_8_phase_kernel(dev, knob, case):
     q = torch.full((case.M + GUARD_ROWS, HD + PAD), NAN, dtype=td, device="cuda")
     kt = torch.full((case.M * HD + 1024,), NAN, dtype=td, device="cuda")
     vt = torch.full((case.M * HD + 1024,), NAN, dtype=td, device="cuda")
-    d = GemmDesc()
-    d.A, d.lda, d.W, d.ldw = A.data_ptr(), case.K + PAD, Wd.data_ptr(), case.K + PAD
-    d.M, d.N, d.K, d.bias, d.epi = case.M, case.N, case.K, bd.data_ptr(), EPI_QKV
-    d.out_T, d.ldc, d.k_tiled, d.vt = q.data_ptr(), HD + PAD, kt.data_ptr(), vt.data_ptr()
-    d.S, d.H, d.Dp, d.q_scale = S, H, ops.DP, Dh ** -0.5 * G.LOG2E
+    d = _desc_ints(case)
+    assert d.epi == EPI_QKV and d.ldc == HD + PAD
+    d.A, d.W, d.bias = A.data_ptr(), Wd.data_ptr(), bd.data_ptr()
+    d.out_T, d.k_tiled, d.vt = q.data_ptr(), kt.data_ptr(), vt.data_ptr()
+    d.q_scale = Dh ** -0.5 * G.LOG2E
     with prof_tags() as p:
         _lib.check(_lib.load().l4p_gemm(_stream(), case.mode, C.byref(d)), "l4p_gemm(qkv)")
     assert launches(p) == [(case.cls, case.tag, 1)], p.lines
@@ -276,10 +273,8 @@ def test_conv_transpose_epilogue_on_the_8_phase_kernel(dev, knob, case):
     A, Wd, bd = _padded(a, 100.0), _padded(w, 100.0, rows=(case.N + 255) // 256 * 256), bias.cuda()
     n_out = case.M * case.N
     out = torch.full((n_out + 1024,), NAN, dtype=td, device="cuda")
-    d = GemmDesc()
-    d.A, d.lda, d.W, d.ldw = A.data_ptr(), case.K + PAD, Wd.data_ptr(), case.K + PAD
-    d.M, d.N, d.K, d.bias, d.epi = case.M, case.N, case.K, bd.data_ptr(), case.epi
-    d.Ti, d.Hi, d.Wi, d.kt, d.kh, d.kw, d.Cout, d.out_T = T, H, W, kt, kh, kw, cout, out.data_ptr()
+    d = _desc_ints(case)
+    d.A, d.W, d.bias, d.out_T = A.data_ptr(), Wd.data_ptr(), bd.data_ptr(), out.data_ptr()
     with prof_tags() as p:
         _lib.check(_lib.load().l4p_gemm(_stream(), case.mode, C.byref(d)), "l4p_gemm(convT)")
     assert launches(p) == [(case.cls, case.tag, 1)], p.lines

@@ -9,13 +9,14 @@ bool g_prof_on = false;
 void prof_begin(int, hipStream_t, const char*) {}
 void prof_end(int, hipStream_t) {}
 void l4p_set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); vfprintf(stderr, fmt, ap); va_end(ap); }
-#define GEMM_PROBE_VARIANTS 1
-#define GEMM_HAS_8P 1
-#include <type_traits>
-#include "../../l4p_amd/csrc/gemm8p.hpp"
-#define GEMM_T bf16_t
-#define GEMM_FN launch_gemm_bf16
-#include "../../l4p_amd/csrc/gemm_launch.inc"
+#define GEMM_PROBE_VARIANTS 1  // (gemm.hpp: g_conv_bt_override)
+#include "../../l4p_amd/csrc/gemm_launch.hpp"
+// the library's knob table reduced to what a stand-alone run needs: L4P_GEMM_VARIANT from the environment, else csrc/prof.hip's defaults
+int knob(int id) {
+    if (id == KNOB_GEMM_VARIANT) return getenv("L4P_GEMM_VARIANT") ? atoi(getenv("L4P_GEMM_VARIANT")) : 0;
+    return id == KNOB_SKINNY_MAX_M ? 128 : id == KNOB_GEMM_4W || id == KNOB_EPI_GENERIC ? 0 : 1;
+}
+static int launch_gemm_bf16(int mode, const GemmParams& p, hipStream_t stream) { return launch_gemm_typed<bf16_t>(mode, p, stream); }
 int main(int argc, char** argv) {
     struct Shape { int B, T, H, W, Cin, Cout; const char* name; } shapes[] = {
         {4, 16, 64, 64, 256, 256, "rcu_64"}, {4, 16, 32, 32, 256, 256, "rcu_32"}, {4, 16, 128, 128, 256, 128, "head1"},

@@ -13,14 +13,8 @@ bool g_prof_on = false;
 void prof_begin(int, hipStream_t, const char*) {}
 void prof_end(int, hipStream_t) {}
 void l4p_set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); vfprintf(stderr, fmt, ap); va_end(ap); }
-#define GEMM_HAS_8P 1
-#include <type_traits>
-#include "../../l4p_amd/csrc/gemm8p.hpp"
-#include "../../l4p_amd/csrc/gemm4w.hpp"
-#include "../../l4p_amd/csrc/conv3_halo.hpp"
-#define GEMM_T bf16_t
-#define GEMM_FN launch_gemm_bf16
-#include "../../l4p_amd/csrc/gemm_launch.inc"
+#define L4P_PROBE_KERNELS 1  // (gemm_launch.hpp then includes gemm4w.hpp)
+#include "../../l4p_amd/csrc/gemm_launch.hpp"
 
 static unsigned short f2bf(float f) { unsigned u; memcpy(&u, &f, 4); return (unsigned short)((u + 0x7FFF + ((u >> 16) & 1)) >> 16); }
 
@@ -69,7 +63,7 @@ int main() {
         {
             GemmParams q = p; q.out_T = C2;
             hipMemset(C, 0, nc * 2); hipMemset(C2, 0, nc * 2);
-            launch_8p<0, 2, 4>(q, 0);
+            launch_8p<bf16_t, 0, 2, 4>(q, 0, GEMM_8P_256x256);
             run4w<0>(p, Gemm4wCfg::LDS_BYTES);
             hipDeviceSynchronize();
             std::vector<unsigned short> h1(nc), h2(nc);
@@ -78,8 +72,8 @@ int main() {
             printf("%-14s [check] %zu / %zu outputs differ between 4w and 8p\n", s.name, bad, nc);
         }
         const int L = Gemm4wCfg::LDS_BYTES, L1 = 150 * 1024;
-        rep("8p 256x256", time_us([&] { launch_8p<0, 2, 4>(p, 0); }));
-        rep("8p 256x256", time_us([&] { launch_8p<0, 2, 4>(p, 0); }));
+        rep("8p 256x256", time_us([&] { launch_8p<bf16_t, 0, 2, 4>(p, 0, GEMM_8P_256x256); }));
+        rep("8p 256x256", time_us([&] { launch_8p<bf16_t, 0, 2, 4>(p, 0, GEMM_8P_256x256); }));
         rep("4w", time_us([&] { run4w<0>(p, L); }));
         rep("4w 1wg/CU", time_us([&] { run4w<0>(p, L1); }));
         rep("4w noepi", time_us([&] { run4w<1>(p, L); }));
@@ -92,7 +86,7 @@ int main() {
         rep("4w pstep4", time_us([&] { run4w<0, 4>(p, L); }));
         rep("4w pstep5", time_us([&] { run4w<0, 5>(p, L); }));
         rep("4w", time_us([&] { run4w<0>(p, L); }));
-        rep("8p 256x256", time_us([&] { launch_8p<0, 2, 4>(p, 0); }));
+        rep("8p 256x256", time_us([&] { launch_8p<bf16_t, 0, 2, 4>(p, 0, GEMM_8P_256x256); }));
         hipFree(A); hipFree(W); hipFree(C); hipFree(C2); hipFree(bias);
     }
     return 0;

@@ -9,14 +9,14 @@ bool g_prof_on = false;
 void prof_begin(int, hipStream_t, const char*) {}
 void prof_end(int, hipStream_t) {}
 void l4p_set_error(const char* fmt, ...) { va_list ap; va_start(ap, fmt); vfprintf(stderr, fmt, ap); va_end(ap); }
-#define GEMM_PROBE_VARIANTS 1
-#define GEMM_HAS_8P 1
-#include <type_traits>
-#include "../../l4p_amd/csrc/gemm8p.hpp"
-#include "../../l4p_amd/csrc/gemm4w.hpp"
-#define GEMM_T bf16_t
-#define GEMM_FN launch_gemm_bf16
-#include "../../l4p_amd/csrc/gemm_launch.inc"
+#define GEMM_PROBE_VARIANTS 1  // (gemm.hpp / gemm8p.hpp: g_tile_gm)
+#include "../../l4p_amd/csrc/gemm_launch.hpp"
+// the library's knob table reduced to what a stand-alone run needs: L4P_GEMM_VARIANT from the environment, else csrc/prof.hip's defaults
+int knob(int id) {
+    if (id == KNOB_GEMM_VARIANT) return getenv("L4P_GEMM_VARIANT") ? atoi(getenv("L4P_GEMM_VARIANT")) : 0;
+    return id == KNOB_SKINNY_MAX_M ? 128 : id == KNOB_GEMM_4W || id == KNOB_EPI_GENERIC ? 0 : 1;
+}
+static int launch_gemm_bf16(int mode, const GemmParams& p, hipStream_t stream) { return launch_gemm_typed<bf16_t>(mode, p, stream); }
 int main(int argc, char** argv) {
     { const int gm = getenv("TILE_GM") ? atoi(getenv("TILE_GM")) : 0; hipMemcpyToSymbol(HIP_SYMBOL(g_tile_gm), &gm, sizeof(int)); }
     struct Shape { int M, N, K; const char* name; } shapes[] = {{2048, 4608, 1408, "qkv"}, {2048, 1408, 1408, "proj"},
@@ -36,7 +36,7 @@ int main(int argc, char** argv) {
         {   // correctness of the selected variant against the plain 128x128 kernel
             void* Cr; hipMalloc(&Cr, nc * 2); hipMemset(Cr, 0, nc * 2); hipMemset(C, 0, nc * 2);
             GemmParams pr = p; pr.out_T = Cr;
-            launch_cfg<128, 128, 0, true>(pr, 0);
+            launch_cfg<bf16_t, 128, 128, 0, true>(pr, 0, GEMM_STAGED_128x128);
             launch_gemm_bf16(0, p, 0);
             hipDeviceSynchronize();
             std::vector<unsigned short> h1(nc), h2(nc);
