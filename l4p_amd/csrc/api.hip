@@ -21,11 +21,6 @@ void l4p_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 
-int launch_layernorm_res(int dtype, const float* x, int x_mod, const void* delta_T, const float* gamma, const float* beta, float eps,
-                         void* out_T, float* out_f32, int M, int C, const float* add, int add_mod, void* out_T2, const float* x_shared,
-                         int x_period, int x_split, hipStream_t stream, float* out_sum = nullptr, const float* part = nullptr,
-                         int nsplit = 0, const float* pbias = nullptr, float* out_stats = nullptr);
-
 extern "C" {
 
 const char* l4p_last_error(void) { return g_err; }

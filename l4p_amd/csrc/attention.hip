@@ -29,9 +29,7 @@
 #include <type_traits>
 
 #include "common.hpp"
-
-int launch_attention64(int dtype, const void* q, const void* kt, const void* vt, void* out, int B, int S, int H, int Dh, float scale,
-                       hipStream_t stream);  // attention64.hip
+#include "launchers.hpp"
 
 __device__ __attribute__((aligned(16))) static const unsigned short g_ones_bf16[8] = {0x3F80, 0x3F80, 0x3F80, 0x3F80,
                                                                                          0x3F80, 0x3F80, 0x3F80, 0x3F80};

@@ -21,6 +21,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "launchers.hpp"
 
 namespace attn64 {
 

@@ -146,6 +146,21 @@ static inline bool dtype_ok(int dtype) { return dtype == L4P_BF16 || dtype == L4
             __VA_ARGS__;                   \
         }                                  \
     } while (0)
+// run `...` with T = the engine type of `dtype`: f16_t / bf16_t, and float for every other code - for launches whose three
+// branches differ in the element type alone (a float branch with another kernel or condition: is16 + L4P_WITH_T16)
+#define L4P_WITH_T(dtype, T, ...)          \
+    do {                                   \
+        if ((dtype) == L4P_F16) {          \
+            typedef f16_t T;               \
+            __VA_ARGS__;                   \
+        } else if ((dtype) == L4P_BF16) {  \
+            typedef bf16_t T;              \
+            __VA_ARGS__;                   \
+        } else {                           \
+            typedef float T;               \
+            __VA_ARGS__;                   \
+        }                                  \
+    } while (0)
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -3,6 +3,7 @@
 #include <cstdlib>
 
 #include "common.hpp"
+#include "launchers.hpp"
 
 // -------------------------------------------------------------------------------------------------
 // Trilinear resize, channels-last [B][Ti][Hi][Wi][C] -> [B][To][Ho][Wo][C].
@@ -314,7 +315,8 @@ int launch_head_out(int dtype, const void* x, const float* w, const float* bias,
     if (is16(dtype)) L4P_WITH_T16(dtype, T16, {
         auto kern = head_out_lds_kernel<T16, 128>;
         const size_t lds = (8 * 128 + 8) * 4 + 256 * 256;
-        HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        static lds_attr_state attr_done;
+        HIP_TRY(lds_attr_once(attr_done, kern, (int)lds));
         hipLaunchKernelGGL(kern, dim3((unsigned)((total + 255) / 256)), dim3(256), lds, stream, (const T16*)x, w, bias, y, vox_per_b,
                            B, Cout, post_exp);
     }); else

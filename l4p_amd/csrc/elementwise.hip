@@ -4,6 +4,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "launchers.hpp"
 
 // ---------------------------------------------------------------------------------------------
 // LayerNorm over the last dim of a float [M][C] residual stream (reference: nn.LayerNorm eps=1e-6
@@ -226,9 +227,7 @@ int launch_layernorm_ex(int dtype, const float* x, const float* gamma, const flo
         return L4P_E_INVALID;
     }
     ProfScope prof(PROF_LAYERNORM, stream, "M%d C%d add%d T2%d act%d f32%d", M, C, add != nullptr, out_T2 != nullptr, act, out_f32 != nullptr);
-    if (is16(dtype)) L4P_WITH_T16(dtype, T16, launch_ln<T16>(x, gamma, beta, eps, out_T, out_f32, M, C, add, add_mod, out_T2, act, stream));
-    else
-        launch_ln<float>(x, gamma, beta, eps, out_T, out_f32, M, C, add, add_mod, out_T2, act, stream);
+    L4P_WITH_T(dtype, T, launch_ln<T>(x, gamma, beta, eps, out_T, out_f32, M, C, add, add_mod, out_T2, act, stream));
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -265,13 +264,11 @@ int launch_layernorm_res(int dtype, const float* x, int x_mod, const void* delta
     if (!part && !out_sum && delta_T && key_ln_tracks_fits(M, C, x_mod, add_mod, add, out_T, out_T2) &&
         (x_mod > 0 ? !x_shared : (!x_shared || x_period == add_mod))) {
         if (x_mod > 0) {
-            if (is16(dtype)) L4P_WITH_T16(dtype, T16, (launch_key_ln_tracks<T16, false>(x, add_mod, nullptr, nullptr, nullptr, nullptr, delta_T, gamma, beta, eps, out_T, out_f32, M, C, add, out_T2, out_stats, stream)));
-            else
-                launch_key_ln_tracks<float, false>(x, add_mod, nullptr, nullptr, nullptr, nullptr, delta_T, gamma, beta, eps, out_T, out_f32, M, C, add, out_T2, out_stats, stream);
+            L4P_WITH_T(dtype, T, (launch_key_ln_tracks<T, false>(x, add_mod, nullptr, nullptr, nullptr, nullptr, delta_T, gamma, beta, eps, out_T,
+                                                                 out_f32, M, C, add, out_T2, out_stats, stream)));
         } else {  // the tracks' own float rows (possibly normalised in place), the common rows of a half-shared layer from x_shared
-            if (is16(dtype)) L4P_WITH_T16(dtype, T16, (launch_key_ln_tracks<T16, false, true>(nullptr, add_mod, nullptr, nullptr, nullptr, nullptr, delta_T, gamma, beta, eps, out_T, out_f32, M, C, add, out_T2, out_stats, stream, x, x_shared, x_split)));
-            else
-                launch_key_ln_tracks<float, false, true>(nullptr, add_mod, nullptr, nullptr, nullptr, nullptr, delta_T, gamma, beta, eps, out_T, out_f32, M, C, add, out_T2, out_stats, stream, x, x_shared, x_split);
+            L4P_WITH_T(dtype, T, (launch_key_ln_tracks<T, false, true>(nullptr, add_mod, nullptr, nullptr, nullptr, nullptr, delta_T, gamma, beta, eps,
+                                                                       out_T, out_f32, M, C, add, out_T2, out_stats, stream, x, x_shared, x_split)));
         }
         HIP_TRY(hipGetLastError());
         return 0;
@@ -288,19 +285,13 @@ int launch_layernorm_res(int dtype, const float* x, int x_mod, const void* delta
 #else
     const float* const part_sel = part;
 #endif
-    if (is16(dtype)) L4P_WITH_T16(dtype, T16, {
+    L4P_WITH_T(dtype, T, {
         if (C <= 512) {
-            if (part_sel) LN_RES_LAUNCH(T16, 2, true); else LN_RES_LAUNCH(T16, 2, false);
+            if (part_sel) LN_RES_LAUNCH(T, 2, true); else LN_RES_LAUNCH(T, 2, false);
         } else {
-            if (part_sel) LN_RES_LAUNCH(T16, 6, true); else LN_RES_LAUNCH(T16, 6, false);
+            if (part_sel) LN_RES_LAUNCH(T, 6, true); else LN_RES_LAUNCH(T, 6, false);
         }
-    }); else {
-        if (C <= 512) {
-            if (part_sel) LN_RES_LAUNCH(float, 2, true); else LN_RES_LAUNCH(float, 2, false);
-        } else {
-            if (part_sel) LN_RES_LAUNCH(float, 6, true); else LN_RES_LAUNCH(float, 6, false);
-        }
-    }
+    });
 #undef LN_RES_LAUNCH
     HIP_TRY(hipGetLastError());
     return 0;
@@ -591,18 +582,14 @@ int launch_layernorm_chain(int dtype, const float* xs, int x_mod, const void* dp
     }
     ProfScope prof(PROF_LAYERNORM, stream, "M%d C%d chain T2%d f32%d", M, C, out_T2 != nullptr, out_f32 != nullptr);
     if (key_ln_tracks_fits(M, C, x_mod, add_mod, add, out_T, out_T2)) {
-        if (is16(dtype)) L4P_WITH_T16(dtype, T16, (launch_key_ln_tracks<T16, true>(xs, x_mod, dprev_T, stats, g0, b0, delta_T, gamma, beta, eps, out_T, out_f32, M, C, add, out_T2, nullptr, stream)));
-        else
-            launch_key_ln_tracks<float, true>(xs, x_mod, dprev_T, stats, g0, b0, delta_T, gamma, beta, eps, out_T, out_f32, M, C, add, out_T2, nullptr, stream);
+        L4P_WITH_T(dtype, T, (launch_key_ln_tracks<T, true>(xs, x_mod, dprev_T, stats, g0, b0, delta_T, gamma, beta, eps, out_T, out_f32, M, C, add,
+                                                            out_T2, nullptr, stream)));
         HIP_TRY(hipGetLastError());
         return 0;
     }
     const dim3 grid((M + 3) / 4);
-    if (is16(dtype)) L4P_WITH_T16(dtype, T16, hipLaunchKernelGGL(layernorm_chain_kernel<T16>, grid, dim3(256), 0, stream, xs, x_mod, (const T16*)dprev_T, stats, g0, b0,
-                           (const T16*)delta_T, gamma, beta, eps, (T16*)out_T, out_f32, M, C, add, add_mod, (T16*)out_T2));
-    else
-        hipLaunchKernelGGL(layernorm_chain_kernel<float>, grid, dim3(256), 0, stream, xs, x_mod, (const float*)dprev_T, stats, g0, b0,
-                           (const float*)delta_T, gamma, beta, eps, (float*)out_T, out_f32, M, C, add, add_mod, (float*)out_T2);
+    L4P_WITH_T(dtype, T, hipLaunchKernelGGL(layernorm_chain_kernel<T>, grid, dim3(256), 0, stream, xs, x_mod, (const T*)dprev_T, stats, g0, b0,
+                                            (const T*)delta_T, gamma, beta, eps, (T*)out_T, out_f32, M, C, add, add_mod, (T*)out_T2));
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -765,9 +752,7 @@ int launch_cast(int dtype, const float* x, void* y, long long n, hipStream_t str
     const long long n4 = n / 4;
     const int grid = (int)((n4 + 255) / 256 < 2048 ? (n4 + 255) / 256 : 2048);
     ProfScope prof(PROF_ELEMENTWISE, stream, "cast");
-    if (is16(dtype)) L4P_WITH_T16(dtype, T16, hipLaunchKernelGGL(cast_kernel<T16>, dim3(grid), dim3(256), 0, stream, x, (T16*)y, n4));
-    else
-        hipLaunchKernelGGL(cast_kernel<float>, dim3(grid), dim3(256), 0, stream, x, (float*)y, n4);
+    L4P_WITH_T(dtype, T, hipLaunchKernelGGL(cast_kernel<T>, dim3(grid), dim3(256), 0, stream, x, (T*)y, n4));
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -818,11 +803,8 @@ int launch_patch_gather(int dtype, const float* rgb, void* out, int B, int Cin, 
     const long long total = (long long)B * (T / pt) * (H / ph) * (W / pw) * Kp;
     const int grid = (int)((total + 255) / 256 < 4096 ? (total + 255) / 256 : 4096);
     ProfScope prof(PROF_ELEMENTWISE, stream, "patch_gather");
-    if (is16(dtype)) L4P_WITH_T16(dtype, T16, hipLaunchKernelGGL(patch_gather_kernel<T16>, dim3(grid), dim3(256), 0, stream, rgb, (T16*)out, B, Cin, T,
-                           H, W, pt, ph, pw, Kp));
-    else
-        hipLaunchKernelGGL(patch_gather_kernel<float>, dim3(grid), dim3(256), 0, stream, rgb, (float*)out, B, Cin, T, H,
-                           W, pt, ph, pw, Kp);
+    L4P_WITH_T(dtype, TT, hipLaunchKernelGGL(patch_gather_kernel<TT>, dim3(grid), dim3(256), 0, stream, rgb, (TT*)out, B, Cin, T, H, W, pt, ph, pw,
+                                             Kp));
     HIP_TRY(hipGetLastError());
     return 0;
 }

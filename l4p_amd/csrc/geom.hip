@@ -1,6 +1,7 @@
 // Small geometry / alignment kernels that the reference runs as torch.linalg calls inside Python
 // loops (with host syncs): window-seam depth alignment and ray-map -> camera pose.
 #include "common.hpp"
+#include "launchers.hpp"
 
 // -------------------------------------------------------------------------------------------------
 // LstSqAffineAligner (aligner.py:29-66): min_{s,t} || s*f(pred) + t - f(target) ||^2, f = safe_inverse

@@ -518,9 +518,6 @@ static void met_launch_dense(hipStream_t s, const MetParams& p, int B, const Met
 
 extern "C" {
 
-int l4p_select_median_dev(l4p_stream s_, const float* x, long long n, int B, const unsigned long long* count, long long count_stride,
-                          unsigned* ws, float* out, long long out_stride);
-
 size_t l4p_metric_ws_bytes(int B, long long n, int mode) {
     if (B < 1 || n < 1 || n > 0x7FFFFFFFll || (long long)B * n > 0x7FFFFFFFll || mode < 0 || mode > L4P_DEPTH_ALIGN_LSTSQ) return 0;
     return met_ws_layout(nullptr, B, n, mode).bytes;

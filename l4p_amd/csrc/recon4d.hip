@@ -356,8 +356,6 @@ int l4p_recon_track_prep(l4p_stream s_, const float* traj, const float* vis_logi
     return 0;
 }
 
-int l4p_select_rank(l4p_stream s_, const float* x, long long n, long long rank, unsigned* ws, float* out);
-
 int l4p_recon_track_scale(l4p_stream s_, const float* ratios, long long n, long long nvis, const int* flag, unsigned* ws,
                           float* sel, float* scale) {
     hipStream_t s = (hipStream_t)s_;

@@ -4,6 +4,7 @@
 // product, the fused (trilinear up-sampling + soft-argmax + spatial means) read-out that never
 // materialises the [N,3,16,224,224] logits, and the integer/boolean sliding-window bookkeeping.
 #include "common.hpp"
+#include "launchers.hpp"
 
 template <typename T> struct Vec8;  // 8 consecutive elements of T as floats
 template <> struct Vec8<bf16_t> {
@@ -1341,6 +1342,24 @@ __global__ __launch_bounds__(256) void t2i_ctx_kernel(const T* __restrict__ prob
 // ------------------------------------------------------------------------------------------------
 #define GRID1D(total, cap) ((int)(((total) + 255) / 256 < (cap) ? ((total) + 255) / 256 : (cap)))
 
+// t2i_attn_kernel<T> with its LDS size: score rows [6][P], the queries [6][96] and 256 floats of scratch; the P.V partial sums
+// [nkg][6][hd] reuse the score rows, and the allocation grows by what they need beyond them (short P)
+template <typename T>
+static int launch_t2i_attn(const void* q, const void* k, const void* v, void* out, int N, int P, int D, int heads, int hd, float scale,
+                           long long kv_stride, const float* pre, long long ld_pre, int pre_heads, hipStream_t stream) {
+    const int ncg = hd / 4, nkg = 256 / ncg;
+    size_t lds = (size_t)(6 * P + 6 * 96 + 256) * 4;
+    const size_t need2 = (size_t)nkg * 6 * hd * 4;
+    if (need2 > (size_t)6 * P * 4) lds += need2 - (size_t)6 * P * 4;
+    auto kern = t2i_attn_kernel<T>;
+    static lds_attr_state attr_done;
+    HIP_TRY(lds_attr_once(attr_done, kern, (int)lds));
+    hipLaunchKernelGGL(kern, dim3(N, heads), dim3(256), lds, stream, (const T*)q, (const T*)k, (const T*)v, (T*)out, P, D, hd, scale,
+                       kv_stride, pre, ld_pre, pre_heads);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 // tokens -> image attention from scores formed elsewhere (folded keys): softmax over the P keys per (track, token, head), then P.V
 int launch_t2i_attn_scores(int dtype, const float* scores, long long ld_scores, const void* v, void* out, int N, int P, int D, int heads,
                            hipStream_t stream) {
@@ -1350,24 +1369,7 @@ int launch_t2i_attn_scores(int dtype, const float* scores, long long ld_scores, 
         return L4P_E_INVALID;
     }
     ProfScope prof(PROF_TRACK, stream, "small_attn kind5 N%d P%d D%d", N, P, D);
-    const int ncg = hd / 4, nkg = 256 / ncg;
-    size_t lds = (size_t)(6 * P + 6 * 96 + 256) * 4;
-    const size_t need2 = (size_t)nkg * 6 * hd * 4;
-    if (need2 > (size_t)6 * P * 4) lds += need2 - (size_t)6 * P * 4;
-    const long long kv_stride = (long long)P * D;
-    if (is16(dtype)) L4P_WITH_T16(dtype, T16, {
-        auto kb = t2i_attn_kernel<T16>;
-        HIP_TRY(hipFuncSetAttribute((const void*)kb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kb, dim3(N, heads), dim3(256), lds, stream, (const T16*)nullptr, (const T16*)nullptr, (const T16*)v,
-                           (T16*)out, P, D, hd, 1.f, kv_stride, scores, ld_scores, heads);
-    }); else {
-        auto kf = t2i_attn_kernel<float>;
-        HIP_TRY(hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        hipLaunchKernelGGL(kf, dim3(N, heads), dim3(256), lds, stream, (const float*)nullptr, (const float*)nullptr, (const float*)v,
-                           (float*)out, P, D, hd, 1.f, kv_stride, scores, ld_scores, heads);
-    }
-    HIP_TRY(hipGetLastError());
-    return 0;
+    L4P_WITH_T(dtype, T, return launch_t2i_attn<T>(nullptr, nullptr, v, out, N, P, D, heads, hd, 1.f, (long long)P * D, scores, ld_scores, heads, stream));
 }
 int launch_i2t_probs(int dtype, const float* s, long long lds_, int pairs, const float* cbias, int rows_per_group, void* p, int ldp,
                      long long M, int heads, int tokens, hipStream_t stream) {
@@ -1377,11 +1379,8 @@ int launch_i2t_probs(int dtype, const float* s, long long lds_, int pairs, const
     }
     ProfScope prof(PROF_TRACK, stream, "i2t_probs");
     const int grid = GRID1D(M * heads, 16384);
-    if (is16(dtype)) L4P_WITH_T16(dtype, T16, hipLaunchKernelGGL(i2t_probs_kernel<T16>, dim3(grid), dim3(256), 0, stream, s, lds_, pairs, cbias, rows_per_group, (T16*)p, ldp, M,
-                           heads, tokens));
-    else
-        hipLaunchKernelGGL(i2t_probs_kernel<float>, dim3(grid), dim3(256), 0, stream, s, lds_, pairs, cbias, rows_per_group, (float*)p, ldp, M, heads,
-                           tokens);
+    L4P_WITH_T(dtype, T, hipLaunchKernelGGL(i2t_probs_kernel<T>, dim3(grid), dim3(256), 0, stream, s, lds_, pairs, cbias, rows_per_group, (T*)p, ldp, M,
+                                            heads, tokens));
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1392,9 +1391,7 @@ int launch_split_hilo(int dtype, const float* in, void* out, int G, int R, long 
     }
     ProfScope prof(PROF_TRACK, stream, "split_hilo");
     const int grid = GRID1D((long long)G * R * C, 16384);
-    if (is16(dtype)) L4P_WITH_T16(dtype, T16, hipLaunchKernelGGL(split_hilo_kernel<T16>, dim3(grid), dim3(256), 0, stream, in, (T16*)out, G, R, C));
-    else
-        hipLaunchKernelGGL(split_hilo_kernel<float>, dim3(grid), dim3(256), 0, stream, in, (float*)out, G, R, C);
+    L4P_WITH_T(dtype, T, hipLaunchKernelGGL(split_hilo_kernel<T>, dim3(grid), dim3(256), 0, stream, in, (T*)out, G, R, C));
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1405,9 +1402,7 @@ int launch_transpose_pad(int dtype, const void* in, void* out, int G, int R, int
     }
     ProfScope prof(PROF_TRACK, stream, "transpose_pad");
     const int grid = GRID1D((long long)G * C * Rp, 16384);
-    if (is16(dtype)) L4P_WITH_T16(dtype, T16, hipLaunchKernelGGL(transpose_pad_kernel<T16>, dim3(grid), dim3(256), 0, stream, (const T16*)in, (T16*)out, G, R, C, Rp));
-    else
-        hipLaunchKernelGGL(transpose_pad_kernel<float>, dim3(grid), dim3(256), 0, stream, (const float*)in, (float*)out, G, R, C, Rp);
+    L4P_WITH_T(dtype, T, hipLaunchKernelGGL(transpose_pad_kernel<T>, dim3(grid), dim3(256), 0, stream, (const T*)in, (T*)out, G, R, C, Rp));
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1433,9 +1428,7 @@ int launch_t2i_probs(int dtype, const float* scores, long long ld_scores, void* 
     }
     ProfScope prof(PROF_TRACK, stream, "t2i_probs");
     const dim3 grid((P + T2I_SPLIT - 1) / T2I_SPLIT, N);
-    if (is16(dtype)) L4P_WITH_T16(dtype, T16, hipLaunchKernelGGL(t2i_probs_kernel<T16>, grid, dim3(192), 0, stream, scores, ld_scores, (T16*)probs, stats, P));
-    else
-        hipLaunchKernelGGL(t2i_probs_kernel<float>, grid, dim3(192), 0, stream, scores, ld_scores, (float*)probs, stats, P);
+    L4P_WITH_T(dtype, T, hipLaunchKernelGGL(t2i_probs_kernel<T>, grid, dim3(192), 0, stream, scores, ld_scores, (T*)probs, stats, P));
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1505,11 +1498,8 @@ int launch_track_keys_init(int dtype, const float* enc, const float* hist, const
     const long long shared8 = shared_from > 0 ? (long long)shared_from * C / 8 : per_q8;  // (0: no shared rows)
     if (shared_from == 0) k32_shared = nullptr;
     ProfScope prof(PROF_TRACK, stream, "track_keys_init");
-    if (is16(dtype)) L4P_WITH_T16(dtype, T16, hipLaunchKernelGGL(track_keys_init_kernel<T16>, dim3(GRID1D(total8, 16384)), dim3(256), 0, stream, enc, hist,
-                           pos, k32, (T16*)kT, (T16*)kP, per_q8, total8, shared8, k32_shared));
-    else
-        hipLaunchKernelGGL(track_keys_init_kernel<float>, dim3(GRID1D(total8, 16384)), dim3(256), 0, stream, enc, hist, pos,
-                           k32, (float*)kT, (float*)kP, per_q8, total8, shared8, k32_shared);
+    L4P_WITH_T(dtype, T, hipLaunchKernelGGL(track_keys_init_kernel<T>, dim3(GRID1D(total8, 16384)), dim3(256), 0, stream, enc, hist, pos, k32,
+                                            (T*)kT, (T*)kP, per_q8, total8, shared8, k32_shared));
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1557,55 +1547,31 @@ int launch_small_attn(int dtype, int kind, const void* q, const void* k, const v
     }
     ProfScope prof(PROF_TRACK, stream, "small_attn kind%d N%d P%d D%d", kind, N, P, D);
     if (kind == 0) {  // 6 x 6 self attention
-        if (is16(dtype)) L4P_WITH_T16(dtype, T16, hipLaunchKernelGGL(self_attn6_kernel<T16>, dim3(N, heads), dim3(64), 0, stream, (const T16*)q,
-                               (const T16*)k, (const T16*)v, (T16*)out, D, hd, scale));
-        else
-            hipLaunchKernelGGL(self_attn6_kernel<float>, dim3(N, heads), dim3(64), 0, stream, (const float*)q,
-                               (const float*)k, (const float*)v, (float*)out, D, hd, scale);
+        L4P_WITH_T(dtype, T, hipLaunchKernelGGL(self_attn6_kernel<T>, dim3(N, heads), dim3(64), 0, stream, (const T*)q, (const T*)k,
+                                                (const T*)v, (T*)out, D, hd, scale));
     } else if (kind == 1 || kind == 3) {  // tokens -> image (3: one K / V set shared by every query)
         const long long kv_stride = kind == 1 ? (long long)P * D : 0;
-        const int ncg = hd / 4, nkg = 256 / ncg;
-        size_t lds = (size_t)(6 * P + 6 * 96 + 256) * 4;
-        const size_t need2 = (size_t)nkg * 6 * hd * 4;
-        if (need2 > (size_t)6 * P * 4) lds += need2 - (size_t)6 * P * 4;
-        auto kf = t2i_attn_kernel<float>;
-        if (is16(dtype)) L4P_WITH_T16(dtype, T16, {
-            auto kb = t2i_attn_kernel<T16>;
-            HIP_TRY(hipFuncSetAttribute((const void*)kb, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(kb, dim3(N, heads), dim3(256), lds, stream, (const T16*)q, (const T16*)k,
-                               (const T16*)v, (T16*)out, P, D, hd, scale, kv_stride, (const float*)nullptr, 0ll, 0);
-        }); else {
-            HIP_TRY(hipFuncSetAttribute((const void*)kf, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-            hipLaunchKernelGGL(kf, dim3(N, heads), dim3(256), lds, stream, (const float*)q, (const float*)k,
-                               (const float*)v, (float*)out, P, D, hd, scale, kv_stride, (const float*)nullptr, 0ll, 0);
-        }
+        L4P_WITH_T(dtype, T, return launch_t2i_attn<T>(q, k, v, out, N, P, D, heads, hd, scale, kv_stride, nullptr, 0, 0, stream));
     } else if (kind == 2 || kind == 4) {  // image -> tokens (4: one query set shared by every track)
         const long long q_stride = kind == 2 ? (long long)P * D : 0;
         if (256 % heads == 0 && (D * (esize_of(dtype))) % 16 == 0) {
             const int rows = 256 / heads, es = esize_of(dtype);
             const size_t lds = (((size_t)12 * D * 4 + 15) & ~(size_t)15) + (size_t)rows * D * es;
             const dim3 grid((P + rows - 1) / rows, N);
-            if (is16(dtype)) L4P_WITH_T16(dtype, T16, {
-                auto kern = i2t_attn_lds_kernel<T16>;
-                HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, (const T16*)q, (const T16*)k, (const T16*)v,
-                                   (T16*)out, P, D, hd, heads, scale, q_stride);
-            }); else {
-                auto kern = i2t_attn_lds_kernel<float>;
-                HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-                hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, (const float*)q, (const float*)k, (const float*)v,
-                                   (float*)out, P, D, hd, heads, scale, q_stride);
-            }
+            L4P_WITH_T(dtype, T, {
+                auto kern = i2t_attn_lds_kernel<T>;
+                static lds_attr_state attr_done;
+                HIP_TRY(lds_attr_once(attr_done, kern, (int)lds));
+                hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, (const T*)q, (const T*)k, (const T*)v, (T*)out, P, D, hd, heads,
+                                   scale, q_stride);
+            });
             HIP_TRY(hipGetLastError());
             return 0;
         }
         const size_t lds = (size_t)12 * D * 4;
         const dim3 grid((P * heads + 255) / 256, N);
-        if (is16(dtype)) L4P_WITH_T16(dtype, T16, hipLaunchKernelGGL(i2t_attn_kernel<T16>, grid, dim3(256), lds, stream, (const T16*)q, (const T16*)k,
-                               (const T16*)v, (T16*)out, P, D, hd, heads, scale, q_stride));
-        else
-            hipLaunchKernelGGL(i2t_attn_kernel<float>, grid, dim3(256), lds, stream, (const float*)q, (const float*)k,
-                               (const float*)v, (float*)out, P, D, hd, heads, scale, q_stride);
+        L4P_WITH_T(dtype, T, hipLaunchKernelGGL(i2t_attn_kernel<T>, grid, dim3(256), lds, stream, (const T*)q, (const T*)k, (const T*)v,
+                                                (T*)out, P, D, hd, heads, scale, q_stride));
     }
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1666,23 +1632,18 @@ int launch_mask_product(int dtype, const void* up, const float* hyper, float* ma
     const size_t lds_tile = ((size_t)3 * Cc * 4 + 15) / 16 * 16 + (size_t)VT * Cc * es;
     if (lds_tile <= 160 * 1024) {
         const dim3 grid((unsigned)((vox + VT - 1) / VT), N);
-        if (is16(dtype)) L4P_WITH_T16(dtype, T16, {
-            auto kern = mask_product_lds_kernel<T16, 128>;
-            HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_tile));
-            hipLaunchKernelGGL(kern, grid, dim3(128), lds_tile, stream, (const T16*)up, hyper, masks, vox, Cc);
-        }); else {
-            auto kern = mask_product_lds_kernel<float, 128>;
-            HIP_TRY(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_tile));
-            hipLaunchKernelGGL(kern, grid, dim3(128), lds_tile, stream, (const float*)up, hyper, masks, vox, Cc);
-        }
+        L4P_WITH_T(dtype, T, {
+            auto kern = mask_product_lds_kernel<T, 128>;
+            static lds_attr_state attr_done;
+            HIP_TRY(lds_attr_once(attr_done, kern, (int)lds_tile));
+            hipLaunchKernelGGL(kern, grid, dim3(128), lds_tile, stream, (const T*)up, hyper, masks, vox, Cc);
+        });
         HIP_TRY(hipGetLastError());
         return 0;
     }
     const dim3 grid(GRID1D(vox, 1024), N);
     const size_t lds = (size_t)3 * Cc * 4;
-    if (is16(dtype)) L4P_WITH_T16(dtype, T16, hipLaunchKernelGGL(mask_product_kernel<T16>, grid, dim3(256), lds, stream, (const T16*)up, hyper, masks, vox, Cc));
-    else
-        hipLaunchKernelGGL(mask_product_kernel<float>, grid, dim3(256), lds, stream, (const float*)up, hyper, masks, vox, Cc);
+    L4P_WITH_T(dtype, T, hipLaunchKernelGGL(mask_product_kernel<T>, grid, dim3(256), lds, stream, (const T*)up, hyper, masks, vox, Cc));
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -349,6 +349,41 @@ def test_mask_product_positioned_input_is_exact(dev, mode, C):
     assert bad.numel() == 0, f"first mismatch (n, m, voxel) {bad[0].tolist()}: got {masks[tuple(bad[0])]}, want {want[tuple(bad[0])]}"
 
 
+def test_dynamic_lds_limit_small_then_over_64k_then_small(dev):
+    """The three kernels whose dynamic LDS size follows the geometry and whose launchers raise MaxDynamicSharedMemorySize through
+    lds_attr_once: each is launched at a small size, at one above the 64 KB default and at the small size again; every launch
+    returns 0 and passes the gate its kernel's parity test uses, whatever ran before in the process (the limit is only ever
+    raised).  Sizes by the launchers' own formulas:
+      * mask_product_lds_kernel, VT = 128: round16(3 C 4) + 128 C es.  C = 8: 96 + 1024 es; bf16 / f16 C = 352: 4224 + 90112 =
+        94336; f32 C = 128: 1536 + 65536 = 67072 (both below the 160 KB switch to the direct kernel).  vox = 130: a ragged tile.
+      * t2i_attn_kernel (kind 1), heads = 1, hd = D = 4: (6 P + 832) 4, plus 256 * 6 * 4 * 4 - 24 P when that is positive.
+        P = 8: 3520 + 24384 = 27904; P = 2688: 67840.
+      * i2t_attn_lds_kernel (kind 2), f32, heads = 1 (256 rows): round16(48 D) + 1024 D.  D = 4: 4288; D = 64: 68608."""
+    for mode in MODES:
+        big_C = 128 if mode == L4P_F32 else 352
+        for C in (8, big_C, 8):
+            N, vox = 2, 130
+            up, upr = as_mode(rnd((N, vox, C), 420), mode)
+            hyper = rnd((N, 3, C), 421, C ** -0.5)
+            check(_mask_product(mode, up, hyper.cuda(), N, vox, C), R.mask_product_ref(upr, hyper), mode, False)
+        for P in (8, 2688, 8):
+            N, D, heads = 1, 4, 1
+            q6, q6r = as_mode(rnd((N, 6, D), 422), mode)
+            kim, kimr = as_mode(rnd((N, P, D), 423), mode)
+            vim, vimr = as_mode(rnd((N, P, D), 424), mode)
+            o1 = sentinel((N, 6, D), ops.torch_dtype(mode))
+            assert _attn(mode, 1, q6, kim, vim, o1, N, P, D, heads) == 0, (mode, P)
+            check(o1, R.small_attn_ref(1, q6r, kimr, vimr, heads), mode, True)
+    for D in (4, 64, 4):
+        N, P, heads = 2, 8, 1
+        qim, qimr = as_mode(rnd((N, P, D), 425), L4P_F32)
+        k6, k6r = as_mode(rnd((N, 6, D), 426), L4P_F32)
+        v6, v6r = as_mode(rnd((N, 6, D), 427), L4P_F32)
+        o2 = sentinel((N, P, D), torch.float32)
+        assert _attn(L4P_F32, 2, qim, k6, v6, o2, N, P, D, heads) == 0, D
+        check(o2, R.small_attn_ref(2, qimr, k6r, v6r, heads), L4P_F32, True)
+
+
 # ------------------------------------------------------------------------------------------------
 # l4p_layernorm_ex
 # ------------------------------------------------------------------------------------------------
