@@ -63,7 +63,8 @@ int l4p_stream_destroy(l4p_stream stream);
 
 /* Dispatch knobs of the launchers (A/B and test aids; the defaults are the shipped configuration).  A knob starts from its
  * environment variable (read ONCE, at first use) and can be changed at run time through l4p_set_knob - no getenv on a launch path.
- *   "conv_halo"  (L4P_CONV_HALO, default 1): 0 = implicit-GEMM forms for every 3x3x3 conv, 1 = the LDS-halo kernel where it fits
+ *   "conv_halo"  (L4P_CONV_HALO, default 1): 0 = implicit-GEMM forms for every 3x3x3 conv, 1 = the LDS-halo kernel where it fits,
+ *                2 = that kernel's predecessor body (two barrier pairs per k-tile; bit-identical to 1, A/B and test aid)
  *   "gemm_4w"    (L4P_GEMM_4W,   default 0): the two-workgroups-per-CU GEMM: 0 never, 1 on the shapes it won, 2 wherever it fits
  *   "maskdot_mfma" (L4P_MASKDOT_MFMA, default 1): L4P_EPI_MASKDOT of the 16-bit engines contracts the activated row with the
  *                hyper-network vectors on the matrix pipe (the row rounded to T first, as the reference's autocast holds it);

@@ -21,16 +21,47 @@
 //    on the lane and on dw only: a lane keeps three fragment base addresses (dw = -1, 0, 1) and a k-tile's eight A
 //    fragment reads are ONE add + immediates.  W tiles are stored in fragment order (LDS row = wave column block * 64 +
 //    j * 16 + MFMA row).  All staging is LDS-DMA with the swizzle applied to the per-lane SOURCE chunk.
-//  * pipeline: the 8-phase kernel's structure with a 32-deep k-tile = two phases of 16 MFMAs per wave
-//        P1: read W(t) + A rows 0-63 | stage W(t+3)        | barrier | 16 MFMAs | barrier
-//        P2: read A rows 64-127      | stage a halo piece  | vmcnt   | barrier | 16 MFMAs | barrier
-//    the two 4-wave groups run one barrier apart (one wave's MFMA segment over its SIMD partner's read / stage
-//    segment).  Hazards: W(t+3) overwrites the slot of W(t-1), last read three barriers earlier by the delayed group;
-//    W(t+1) is waited for (vmcnt(2 * W_PASS): everything but the two youngest W tiles; halo pieces in flight only make
-//    the wait stricter) at the end of P2(t) and first read after the following barrier; a halo plane is refilled >= 4
-//    barriers after its last read and first read >= 6 k-tiles after its refill was issued.
+//  * pipeline: the 8-phase kernel's two-group ping-pong with ONE phase per k-tile (= tap): 32 MFMAs per wave and barrier pair
+//        R(t): read W(t) + all eight A fragments | stage W(t+3) | stage the halo piece due | vmcnt, lgkmcnt(0) | barrier
+//        M(t): 32 MFMAs | barrier
+//    The 27 taps of a channel slice are unrolled: (dt, dh, dw), the halo piece due at a tap and the seam of the staged k range
+//    are compile-time; a tap's A reads are one of three per-dw base registers + immediates (< 64 KB from the wave's
+//    (dt, dh) = (-1, -1) corner); what stays run-time per tap is the W ring slot (27 k-tiles per slice rotate a 4-slot ring by
+//    three), the k offset of W(t+3), and the two slice-uniform branches "not the first / not the last slice" around the halo
+//    pieces.  The predecessor (conv3_halo2p_kernel, knob conv_halo = 2, and the only body of the UPS loader) cut the same k-tile
+//    into two phases of 16 MFMAs with a barrier pair each and walked the taps with run-time counters: 1.49 scalar instructions per
+//    MFMA against 0.35 here, the matrix pipe busy 60 % of the cycles against 78 %.  Both bodies give every
+//    accumulator the same k-tiles in the same order: bit-identical (tests/test_conv3_halo_phases_gpu.py).
+//  * hazards of the one-phase body.  Barriers are numbered per workgroup; the two 4-wave groups run one barrier apart: group 0
+//    runs R(t) before barrier 2t and M(t) between 2t and 2t+1, group 1 runs R(t) between 2t and 2t+1 and M(t) between 2t+1 and
+//    2t+2 (a wave's MFMA segment lies over its SIMD partner's read / stage segment).  Every R ends with lgkmcnt(0) BEFORE its
+//    barrier: a wave's LDS reads have returned when it arrives, so a write issued by anyone after that barrier cannot overtake
+//    them - with half the barriers of the predecessor the distances below are ONE barrier where they were three or four, and this
+//    wait is what makes one enough.
+//      - ring slot (t+3) & 3 held W(t-1), last read by the delayed group in its R(t-1), which ends before barrier 2t-1; the
+//        earliest W(t+3) is issued by group 0 in R(t), after barrier 2t-1.  Group 1's own W(t+3) goes out after barrier 2t;
+//        group 0 finished reading W(t-1) before barrier 2t-2.
+//      - W(t+1): vmcnt(2 * W_PASS) at the end of R(t) leaves only the 2 * W_PASS youngest operations of the wave in flight - at
+//        most W(t+3), W(t+2) (a halo piece issued behind W(t+3) only makes the wait stricter) - so the wave's part of W(t+1) has
+//        landed before its barrier (2t for group 0, 2t+1 for group 1); both groups read W(t+1) only after barrier 2t+1.
+//      - halo planes: plane 0 is read by taps 0-8, plane 1 by taps 0-17, plane 2 by taps 9-26, plane 3 by taps 18-26.  The next
+//        slice's plane 0 / 1 goes out from R(9) / R(18) on: the delayed group's reads of tap 8 / 17 returned before the barrier in
+//        front of group 0's R(9) / R(18).  This slice's planes 2 / 3 go out in R(0) .. R(2 * H_PASS - 1): the last reads of the
+//        previous slice's tap 26 returned before the barrier in front of group 0's R(0).  A piece issued in R(t) is among the
+//        landed operations of the wave's wait in R(t+2) at the latest (each tap issues at least W_PASS operations behind it) and
+//        visible to every wave one barrier later; the first read of a refilled plane is >= 6 k-tiles after its last piece went
+//        out (plane 1 of the next slice: issued by tap 20, read at the next tap 0; plane 2: by tap 2, read at tap 9).
+//      - the LDS-DMA queue is never drained: no wait in the loop is vmcnt(0).
 #pragma once
+#include <utility>
+
 #include "gemm.hpp"
+
+// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index is a compile-time constant in its body
+template <int... I, typename F>
+__device__ __forceinline__ void conv_halo_static_for(std::integer_sequence<int, I...>, F&& f) {
+    (f(std::integral_constant<int, I>{}), ...);
+}
 
 template <int WR, int WC>
 struct ConvHaloCfg {
@@ -53,9 +84,12 @@ struct ConvHaloCfg {
 // landed behind that k-tile's MFMAs - forms sum w_ab * v_ab in the order and with the rounding of upsample_line (dpt_ops.hip: the
 // fused conv equals up-sample + conv bit for bit) and writes the 16 bytes into the halo with ds_write_b128.  The refill schedule and
 // its hazards are the copy form's with every write one k-tile later (later than a plane's last read, >= 5 k-tiles before its first).
-template <typename T, int WR, int WC, bool UPS = false>
-__global__ __launch_bounds__(512) void conv3_halo_kernel(const GemmParams p) {
+// PHASES: barrier pairs per k-tile of the main loop - 1 = one phase of 32 MFMAs per tap (conv3_halo_kernel), 2 = the predecessor's two
+// phases of 16 (conv3_halo2p_kernel: knob conv_halo = 2, and the only body of the UPS loader).  Everything but the main loop is shared.
+template <typename T, int WR, int WC, bool UPS, int PHASES>
+__device__ __forceinline__ void conv3_halo_body(const GemmParams& p) {
     static_assert(WR * WC == 8 && (WC == 2 || WC == 4), "8 waves");
+    static_assert(PHASES == 2 || (PHASES == 1 && !UPS), "the fused up-sampling loader is scheduled for the two-phase body");
     typedef ConvHaloCfg<WR, WC> Cfg;
     constexpr int BM = Cfg::BM, BN = Cfg::BN, TM = 8, TN = 4;
     constexpr int TT = Cfg::TT, TH = Cfg::TH, TW = Cfg::TW, HH = Cfg::HH, HW = Cfg::HW, PR = Cfg::PR, PRP = Cfg::PRP;
@@ -247,9 +281,9 @@ __global__ __launch_bounds__(512) void conv3_halo_kernel(const GemmParams p) {
     for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int j = 0; j < TN; ++j) acc[i][j] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    vec8<T> xa[4], wb[4];
+    vec8<T> xa[PHASES == 1 ? 8 : 4], wb[4];
 
-    auto read_w = [&](int t) {
+    auto read_w = [&](int t) {  // t: the k-tile, or any number equal to it modulo 4
         const char* base = wring + (t & 3) * WSLOT + w_off;
 #pragma unroll
         for (int j = 0; j < 4; ++j) wb[j] = *(const vec8<T>*)(base + j * 1024);
@@ -305,6 +339,13 @@ __global__ __launch_bounds__(512) void conv3_halo_kernel(const GemmParams p) {
     if (grp == 1) __builtin_amdgcn_s_barrier();  // second wave group runs one barrier behind
     __builtin_amdgcn_sched_barrier(0);
 
+    if constexpr (PHASES == 2) {
+    // ---- the predecessor: a k-tile as two phases of 16 MFMAs per wave, taps walked with run-time counters
+    //        P1: read W(t) + A rows 0-63 | stage W(t+3)        | barrier | 16 MFMAs | barrier
+    //        P2: read A rows 64-127      | stage a halo piece  | vmcnt   | barrier | 16 MFMAs | barrier
+    //      Hazards: W(t+3) overwrites the slot of W(t-1), last read three barriers earlier by the delayed group; W(t+1) is waited
+    //      for (vmcnt(2 * W_PASS)) at the end of P2(t) and first read after the following barrier; a halo plane is refilled >= 4
+    //      barriers after its last read and first read >= 6 k-tiles after its refill was issued ----
     int tap = 0, cs = 0;          // k-tile t = cs * 27 + tap = tap (dt, dh, dw) of channel slice cs
     int dw = 0, dh = 0;           // dw + 1, dh + 1 of the tap
     int toff = (-PRP - HW) * 64;  // byte offset of the tap's (dt, dh) rows relative to the centre (dw is in a_base)
@@ -379,6 +420,73 @@ __global__ __launch_bounds__(512) void conv3_halo_kernel(const GemmParams p) {
             koff3 += 64 - 27 * tap_bytes;
         }
     }
+    } else {
+        // ---- one phase per tap; the 27 taps of a slice are unrolled: (dt, dh, dw), the halo piece due and the seam of the staged
+        //      k range are compile-time, the fragment addresses are three bases (one per dw) + immediates (< 64 KB from the wave's
+        //      (dt, dh) = (-1, -1) corner: (2 * PRP + 2 * HW + 7 * HW) * 64 = 53376 for the 512-row tile) ----
+        static_assert((2 * PRP + 9 * HW) * 64 + 48 < 65536, "ds_read immediates");
+        int a_lo[3];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) {
+            a_lo[d] = a_base[d] + (-PRP - HW) * 64;
+            asm volatile("" : "+v"(a_lo[d]));  // (opaque: the optimiser re-associated the taps' offsets onto another base, with negative
+                                               //  offsets that are no immediates - an address register per fragment and tap)
+        }
+        auto stage_halo_pass = [&](int plane, int cs, auto I) {  // pass I (compile-time) of a plane: one LDS-DMA instruction per lane
+            constexpr int i = decltype(I)::value;
+            if (i * 512 + wave * 64 >= PRP * 4) return;  // (whole waves past the plane issue nothing: wave-uniform)
+            const int gt = t0 - 1 + plane;
+            const bool ok = h_ok[i] && (unsigned)gt < (unsigned)p.Ti;
+            long long sbase = ((long long)bb * p.Ti + gt) * plane_bytes + cs * 64;  // scalar: the (b, t) plane and the slice
+            asm volatile("" : "+s"(sbase));  // (opaque: else the per-lane 64-bit address of every (plane, pass) is kept across the loop)
+            const char* src = ok ? (const char*)p.A + sbase + h_off[i] : zero;
+            __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(smem + (plane * PRP * 4 + i * 512 + wave * 64) * 16), 16, 0, 0);
+        };
+        int ws = 0;                    // ring slot of W(t): t & 3
+        int koff3 = 3 * tap_bytes;     // byte offset of the k range of k-tile t + 3
+        for (int cs = 0; cs < ncs; ++cs) {
+            const bool more = cs + 1 < ncs;
+            conv_halo_static_for(std::make_integer_sequence<int, 27>{}, [&](auto TAP) {
+                constexpr int tap = decltype(TAP)::value, dt = tap / 9, dh = tap / 3 % 3, dw = tap % 3;
+                constexpr int aoff = (dt * PRP + dh * HW) * 64;
+                read_w(ws);
+#pragma unroll
+                for (int f = 0; f < 8; ++f) xa[f] = *(const vec8<T>*)(smem + a_lo[dw] + (aoff + f * (HW * 64)));
+                // W(t+3) into the slot of W(t-1); past the last k-tile: zero-chunk dummies (the counted waits stay uniform)
+#pragma unroll
+                for (int i = 0; i < W_PASS; ++i) {
+                    const char* src = (tap + 3 < 27 || more) ? w_src[i] + koff3 : zero;
+                    __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(wring + ((ws + 3) & 3) * WSLOT + (i * 512 + wave * 64) * 16), 16, 0, 0);
+                }
+                // the halo piece due at this tap: this slice's planes 2 / 3 (first read at tap 9 / 18), the next slice's planes 0 / 1
+                // once the current slice no longer reads them
+                if constexpr (tap < H_PASS) {
+                    if (cs > 0) stage_halo_pass(2, cs, std::integral_constant<int, tap>{});
+                } else if constexpr (tap < 2 * H_PASS) {
+                    if (cs > 0) stage_halo_pass(3, cs, std::integral_constant<int, tap - H_PASS>{});
+                } else if constexpr (tap >= 9 && tap < 9 + H_PASS) {
+                    if (more) stage_halo_pass(0, cs + 1, std::integral_constant<int, tap - 9>{});
+                } else if constexpr (tap >= 18 && tap < 18 + H_PASS) {
+                    if (more) stage_halo_pass(1, cs + 1, std::integral_constant<int, tap - 18>{});
+                }
+                // W(t+1) (and everything older) has landed, and this wave's LDS reads have RETURNED: whatever another wave writes
+                // after the barrier (W(t+3), a halo plane) cannot overtake them
+                asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(2 * W_PASS) : "memory");
+                bar();
+                __builtin_amdgcn_s_setprio(1);
+#pragma unroll
+                for (int f = 0; f < 8; ++f)
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) acc[f][j] = mma16(wb[j], xa[f], acc[f][j]);
+                __builtin_amdgcn_s_setprio(0);
+                bar();
+                ws = (ws + 1) & 3;
+                koff3 += tap_bytes;
+                asm volatile("" : "+s"(koff3));  // (a running sum, not 27 multiples of tap_bytes held in scalar registers)
+                if constexpr (tap == 23) koff3 += 64 - 27 * tap_bytes;  // k-tile t + 3 is tap 0 of the next slice: back by 27 taps, on by 32 channels
+            });
+        }
+    }
     if (grp == 0) __builtin_amdgcn_s_barrier();  // pairs with the trailing barrier of the delayed group
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (only zero-chunk dummies are still in flight)
 
@@ -393,4 +501,15 @@ __global__ __launch_bounds__(512) void conv3_halo_kernel(const GemmParams p) {
         return origin + (long long)(f / TH) * hw_out + (f % TH) * Wo + (r & 15);
     };
     gemm_epilogue_dense_cases<T, TM, TN>(p, acc, m_tile + wr * 128, wc * 64, li, kg, rowmap);
+}
+
+// the default body (one phase per tap); UPS stays a parameter of the name: the probe-only loader is conv3_halo2p_kernel<.., true>
+template <typename T, int WR, int WC, bool UPS = false>
+__global__ __launch_bounds__(512) void conv3_halo_kernel(const GemmParams p) {
+    conv3_halo_body<T, WR, WC, UPS, 1>(p);
+}
+// the predecessor (two phases of 16 MFMAs per k-tile): knob conv_halo = 2, and the fused up-sampling loader
+template <typename T, int WR, int WC, bool UPS = false>
+__global__ __launch_bounds__(512) void conv3_halo2p_kernel(const GemmParams p) {
+    conv3_halo_body<T, WR, WC, UPS, 2>(p);
 }

@@ -164,12 +164,13 @@ static int launch_4w(const GemmParams& p, hipStream_t stream, GemmForm form) {
 #endif
 
 // LDS-halo 3x3x3 conv (conv3_halo.hpp)
-template <typename T, int WR, int WC, bool UPS = false>
+template <typename T, int WR, int WC, bool UPS = false, bool TWO_PHASE = UPS>
 static int launch_halo(const GemmParams& p, hipStream_t stream, GemmForm form) {
     typedef ConvHaloCfg<WR, WC> Cfg;
     typedef ConvHaloTile<WR, WC> Tile;  // (what conv_halo_fits checked the volume against)
     static_assert(Cfg::BM == Tile::BM && Cfg::BN == Tile::BN && Cfg::TT == Tile::TT && Cfg::TH == Tile::TH && Cfg::TW == Tile::TW, "gemm_select.hpp");
-    auto kern = conv3_halo_kernel<T, WR, WC, UPS>;
+    static_assert(TWO_PHASE || !UPS, "the fused up-sampling loader exists on the two-phase body only");
+    auto kern = TWO_PHASE ? conv3_halo2p_kernel<T, WR, WC, UPS> : conv3_halo_kernel<T, WR, WC, false>;
     static lds_attr_state attr_done;
     HIP_TRY(lds_attr_once(attr_done, kern, Cfg::LDS_BYTES));
     ProfScope prof = gemm_prof(PROF_CONV3D, stream, p, p.K, form);
@@ -227,6 +228,8 @@ static int launch_form(GemmForm form, const GemmParams& p, hipStream_t stream) {
             case GEMM_8P_CONV: return launch_8p<T, 1, 2, 4>(p, stream, form);
             case GEMM_HALO_2x4: return launch_halo<T, 2, 4>(p, stream, form);
             case GEMM_HALO_4x2: return launch_halo<T, 4, 2>(p, stream, form);
+            case GEMM_HALO_2x4_2P: return launch_halo<T, 2, 4, false, true>(p, stream, form);
+            case GEMM_HALO_4x2_2P: return launch_halo<T, 4, 2, false, true>(p, stream, form);
             case GEMM_SKINNY: return launch_skinny<T, false>(p, stream, form);
             case GEMM_SKINNY_WGRP: return launch_skinny<T, true>(p, stream, form);
             case GEMM_SUBPIX_8P: return launch_8p_subpixel<T>(p, stream, form);

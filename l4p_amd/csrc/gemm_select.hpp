@@ -36,9 +36,12 @@ enum GemmForm {
     GEMM_8P_SK_256x256,
     GEMM_8P_SK_256x192,
     GEMM_8P_CONV,
-    // LDS-halo 3x3x3 conv (conv3_halo.hpp), 16-bit: ConvHaloCfg<2, 4>, <4, 2>, and <4, 2> with the up-sampling loader (probe builds)
+    // LDS-halo 3x3x3 conv (conv3_halo.hpp), 16-bit: ConvHaloCfg<2, 4>, <4, 2>; their predecessor body with two phases per k-tile
+    // (conv_halo = 2); and <4, 2> with the up-sampling loader (probe builds)
     GEMM_HALO_2x4,
     GEMM_HALO_4x2,
+    GEMM_HALO_2x4_2P,
+    GEMM_HALO_4x2_2P,
     GEMM_HALO_4x2_UPS,
     // one-wave kernel (gemm_skinny.hpp), 16-bit: plain and with row-grouped weights
     GEMM_SKINNY,
@@ -84,6 +87,8 @@ inline const char* gemm_form_tag(GemmForm form, int nsplit, char (&buf)[GEMM_TAG
         case GEMM_8P_CONV: return "8p t256x256";
         case GEMM_HALO_2x4: return "halo t256x256";
         case GEMM_HALO_4x2: return "halo t512x128";
+        case GEMM_HALO_2x4_2P: return "halo 2p t256x256";
+        case GEMM_HALO_4x2_2P: return "halo 2p t512x128";
         case GEMM_HALO_4x2_UPS: return "halo ups t512x128";
         case GEMM_SKINNY: return "skinny";
         case GEMM_SKINNY_WGRP: return "wgrp skinny";
@@ -254,11 +259,12 @@ inline GemmForm gemm_select(int mode, int esize, const l4p_gemm_desc& p, const G
             *err = "conv3d: the fused up-sampling loader takes N == 128, stride 1, Cin % 32 == 0, whole 2 x 16 x 16 output blocks";
             return GEMM_FORM_INVALID;
         }
-        // L4P_CONV_HALO=0: the implicit-GEMM forms for every conv (A/B aid; l4p_set_knob("conv_halo", ..): the tests switch forms
-        // inside one process)
+        // L4P_CONV_HALO=0: the implicit-GEMM forms for every conv; 2: the LDS-halo kernel's predecessor body, two phases of 16 MFMAs
+        // per k-tile - bit-identical to the default's one phase of 32 (A/B aids; l4p_set_knob("conv_halo", ..): the tests switch
+        // forms inside one process)
         if (mode == 1 && k.conv_halo && variant != 1) {
-            if (conv_halo_fits<2, 4>(p)) return GEMM_HALO_2x4;
-            if (conv_halo_fits<4, 2>(p)) return GEMM_HALO_4x2;
+            if (conv_halo_fits<2, 4>(p)) return k.conv_halo == 2 ? GEMM_HALO_2x4_2P : GEMM_HALO_2x4;
+            if (conv_halo_fits<4, 2>(p)) return k.conv_halo == 2 ? GEMM_HALO_4x2_2P : GEMM_HALO_4x2;
         }
         if (p.splitk > 1 && mode == 0 && !p.relu_in && p.K % 8 == 0 && variant != 1 && p.N > 128) {
             // split-K on 256x256 tiles when the slices fill most of the chip exactly once (the batch-1 MLP-out projection:
