@@ -719,7 +719,9 @@ int l4p_t2i_context(l4p_stream stream, int dtype, const void* probs_T, const flo
 
 /* Fused read-out (sparse_heads.py:572-589,645-647): trilinear (align_corners=False) resize of masks
  * [N][3][T][h][w] to H x W, soft-argmax of channel 0 (traj [N][2][T]), spatial mean of channel 1
- * (vis [N][T]) and exp(mean) of channel 2 (depth [N][T]); the up-sampled logits are never stored. */
+ * (vis [N][T]) and exp(mean) of channel 2 (depth [N][T]); the up-sampled logits are never stored.  The soft-argmax is the
+ * reference's (torch.softmax of the up-sampled map) for any finite logits, however peaked.  L4P_E_INVALID, with nothing
+ * launched, for a null pointer, a size < 1, or source maps (3 h w + w + h floats) that do not fit one workgroup's LDS. */
 int l4p_track_readout(l4p_stream stream, const float* masks, float* traj, float* vis, float* depth, int N, int T,
                       int h, int w, int H, int W);
 

@@ -181,6 +181,9 @@ __device__ __forceinline__ float wave_max(float v) {
 // the full-size model asks for later).  
 #include <atomic>
 #include <mutex>
+// The LDS of one gfx950 workgroup, static and dynamic together: the most hipFuncSetAttribute grants.  Launchers that choose a kernel
+// form by its LDS request, or refuse a geometry, compare against this.
+constexpr size_t LDS_DEVICE_LIMIT = 160 * 1024;
 struct lds_attr_state {
     std::atomic<int> set[64] = {};
     std::mutex mu;  // raising the limit is serialised, so a smaller request can never overwrite a larger one

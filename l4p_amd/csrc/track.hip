@@ -628,6 +628,20 @@ __device__ __forceinline__ void src_idx_nc(int dst, int in, int out, int& i0, in
     i1 = i0 + (i0 < in - 1 ? 1 : 0);
 }
 
+// The soft-argmax's shift.  Softmax is shift-invariant, so any shift that keeps the exponents non-positive and the sum z of the samples'
+// exponentials far from underflow gives the reference's value.  Pass 1 takes max(source): bilinear interpolation is a convex
+// combination, so it bounds the up-sampled maximum from ABOVE - but it is attained only where an output sample falls on the source
+// maximum.  An isolated peak between the samples of a 4x resize reaches weight 0.875^2 at best (largest exponent -0.234 (peak -
+// neighbours)), and a down-sampling grid can skip the source maximum altogether: for peaked logits every exponential underflows, z = 0
+// and sx / z is NaN.  With the TRUE up-sampled maximum as the shift the largest sample is exp(0), so z >= 1; with max(source) it is
+// z_true * exp(max(up) - max(source)).  z < READOUT_Z_MIN = 2^-64 therefore says that the bound overshot by more than 64 ln 2 = 44.4,
+// and the workgroup (z is block-uniform) takes the rare path: one walk for the exact max(lerp2) over the H x W samples, then pass 2
+// again with it.  While z >= 2^-64 the largest sample is >= 2^-64 / (H W) >= 2^-94 for H W <= 2^30, and every sample a float sum can still
+// see beside it (>= 2^-24 of it, i.e. >= 2^-118) is a normal float above 2^-126: nothing that matters was flushed or denormal, and the
+// common path's result stands as it was, bit for bit.  The exact maximum is a max over the same lerp2 values in both kernels (order
+// does not matter to a max), so the two forms agree bit for bit on the rare path as well.
+constexpr float READOUT_Z_MIN = 0x1p-64f;
+
 // A thread owns output columns x = tid, tid + 256, ... and walks down the rows: its x source indices / weight stay in
 // registers and the row's y indices / weight are wave-uniform, so a sample is 4 LDS reads + 3 lerps (the flat-index form
 // recomputed two source indices and an integer division per sample and was VALU-bound: 242 us per clip).
@@ -649,9 +663,8 @@ __global__ __launch_bounds__(256) void track_readout_kernel(const float* __restr
         const float bot = (1.f - lx) * b[r1 + x0] + lx * b[r1 + x1];
         return (1.f - ly) * top + ly * bot;
     };
-    // pass 1: an upper bound of channel 0 and the spatial sums of the up-sampled channels 1 and 2, all from the 64 x 64 source.
-    // Bilinear interpolation is a convex combination, so max(source) bounds the up-sampled maximum - the soft-argmax below only
-    // needs its exponents non-positive (softmax is shift-invariant) -, and the sum of an up-sampled channel is
+    // pass 1: an upper bound of channel 0 (max(source) >= the up-sampled maximum; not tight, see READOUT_Z_MIN) and the spatial sums of
+    // the up-sampled channels 1 and 2, all from the 64 x 64 source.  The sum of an up-sampled channel is
     // sum_r b[r] * wy[row(r)] * wx[col(r)] with wx[i] / wy[i] = the total weight source column / row i receives from the W / H
     // output positions (accumulated per source index in a fixed order).  Replaces a second walk over all H x W samples of
     // three channels (12 LDS reads + 9 lerps per sample): 171 -> ~90 us per 64-track window.
@@ -691,38 +704,61 @@ __global__ __launch_bounds__(256) void track_readout_kernel(const float* __restr
     s1 = red[0][1] + red[1][1] + red[2][1] + red[3][1];
     s2 = red[0][2] + red[1][2] + red[2][2] + red[3][2];
     __syncthreads();
-    // pass 2: soft-argmax
-    float z = 0.f, sx = 0.f, sy = 0.f;
-    for (int x = tid; x < W; x += 256) {
-        int x0, x1;
-        float lx;
-        src_idx_nc(x, w, W, x0, x1, lx);
-        const float xc = (float)x + 0.5f;
-        for (int y = 0; y < H; ++y) {
-            int y0, y1;
-            float ly;
-            src_idx_nc(y, h, H, y0, y1, ly);
-            // (expf, not v_exp_f32: the bare instruction is 13 us per launch faster, but its last-ulp differences moved one
-            //  re-seeded query of the 4-window full-size bf16 run onto another frame - the track then differs by 7e-2 in depth)
-            const float e = expf(lerp2(lo, y0 * w, y1 * w, x0, x1, lx, ly) - mx);
-            z += e;
-            sx += e * xc;
-            sy += e * ((float)y + 0.5f);
+    // pass 2: soft-argmax (a second time with the exact maximum when the first sum says that max(source) overshot: READOUT_Z_MIN)
+    float z, sx, sy;
+    for (int exact = 0;; ++exact) {
+        z = 0.f, sx = 0.f, sy = 0.f;
+        for (int x = tid; x < W; x += 256) {
+            int x0, x1;
+            float lx;
+            src_idx_nc(x, w, W, x0, x1, lx);
+            const float xc = (float)x + 0.5f;
+#pragma unroll 2  // (two independent expf chains per trip, the sums in row order as before)
+            for (int y = 0; y < H; ++y) {
+                int y0, y1;
+                float ly;
+                src_idx_nc(y, h, H, y0, y1, ly);
+                // (expf, not v_exp_f32: the bare instruction is 13 us per launch faster, but its last-ulp differences moved one
+                //  re-seeded query of the 4-window full-size bf16 run onto another frame - the track then differs by 7e-2 in depth)
+                const float e = expf(lerp2(lo, y0 * w, y1 * w, x0, x1, lx, ly) - mx);
+                z += e;
+                sx += e * xc;
+                sy += e * ((float)y + 0.5f);
+            }
         }
-    }
-    z = wave_sum(z);
-    sx = wave_sum(sx);
-    sy = wave_sum(sy);
-    if ((tid & 63) == 0) {
-        red[tid >> 6][0] = z;
-        red[tid >> 6][1] = sx;
-        red[tid >> 6][2] = sy;
-    }
-    __syncthreads();
-    if (tid == 0) {
+        z = wave_sum(z);
+        sx = wave_sum(sx);
+        sy = wave_sum(sy);
+        if ((tid & 63) == 0) {
+            red[tid >> 6][0] = z;
+            red[tid >> 6][1] = sx;
+            red[tid >> 6][2] = sy;
+        }
+        __syncthreads();
         z = red[0][0] + red[1][0] + red[2][0] + red[3][0];
         sx = red[0][1] + red[1][1] + red[2][1] + red[3][1];
         sy = red[0][2] + red[1][2] + red[2][2] + red[3][2];
+        if (exact || z >= READOUT_Z_MIN) break;  // block-uniform: every thread has read the same four partial sums
+        __syncthreads();
+        float m2 = -INFINITY;
+        for (int x = tid; x < W; x += 256) {
+            int x0, x1;
+            float lx;
+            src_idx_nc(x, w, W, x0, x1, lx);
+            for (int y = 0; y < H; ++y) {
+                int y0, y1;
+                float ly;
+                src_idx_nc(y, h, H, y0, y1, ly);
+                m2 = fmaxf(m2, lerp2(lo, y0 * w, y1 * w, x0, x1, lx, ly));
+            }
+        }
+        m2 = wave_max(m2);
+        if ((tid & 63) == 0) red[tid >> 6][0] = m2;
+        __syncthreads();
+        mx = fmaxf(fmaxf(red[0][0], red[1][0]), fmaxf(red[2][0], red[3][0]));
+        __syncthreads();
+    }
+    if (tid == 0) {
         traj[((long long)n * 2 + 0) * T + t] = sx / z;
         traj[((long long)n * 2 + 1) * T + t] = sy / z;
         vis[(long long)n * T + t] = s1 / (float)(H * W);
@@ -811,42 +847,61 @@ __global__ __launch_bounds__(1024) void track_readout_wide_kernel(const float* _
     s1 = red[0][1] + red[1][1] + red[2][1] + red[3][1];
     s2 = red[0][2] + red[1][2] + red[2][2] + red[3][2];
     __syncthreads();
-    // pass 2: soft-argmax
-    float z = 0.f, sx = 0.f, sy = 0.f;
+    // pass 2: soft-argmax (a second time with the exact maximum when the first sum says that max(source) overshot: READOUT_Z_MIN)
+    float z, sx, sy;
     const float xc = (float)tid + 0.5f;
-    for (int yb = 0; yb < H; yb += READOUT_RB) {
-        const int rows = H - yb < READOUT_RB ? H - yb : READOUT_RB;
-        for (int i = tid; i < rows * W; i += 1024) {
-            const int yy = i / W, x = i - yy * W;
-            const int px = tx0[x], py = ty0[yb + yy];
-            eb[i] = expf(lerp2(lo, py & 0xFFFF, py >> 16, px & 0xFFFF, px >> 16, tlx[x], tly[yb + yy]) - mx);
+    for (int exact = 0;; ++exact) {
+        z = 0.f, sx = 0.f, sy = 0.f;
+        for (int yb = 0; yb < H; yb += READOUT_RB) {
+            const int rows = H - yb < READOUT_RB ? H - yb : READOUT_RB;
+            for (int i = tid; i < rows * W; i += 1024) {
+                const int yy = i / W, x = i - yy * W;
+                const int px = tx0[x], py = ty0[yb + yy];
+                eb[i] = expf(lerp2(lo, py & 0xFFFF, py >> 16, px & 0xFFFF, px >> 16, tlx[x], tly[yb + yy]) - mx);
+            }
+            __syncthreads();
+            if (tid < W) {
+#pragma unroll 8  // (eight LDS reads in flight per trip, the sums in row order as before)
+                for (int yy = 0; yy < rows; ++yy) {
+                    const float e = eb[yy * W + tid];
+                    z += e;
+                    sx += e * xc;
+                    sy += e * ((float)(yb + yy) + 0.5f);
+                }
+            }
+            __syncthreads();
         }
-        __syncthreads();
-        if (tid < W) {
-            for (int yy = 0; yy < rows; ++yy) {
-                const float e = eb[yy * W + tid];
-                z += e;
-                sx += e * xc;
-                sy += e * ((float)(yb + yy) + 0.5f);
+        if (tid < 256) {
+            z = wave_sum(z);
+            sx = wave_sum(sx);
+            sy = wave_sum(sy);
+            if ((tid & 63) == 0) {
+                red[tid >> 6][0] = z;
+                red[tid >> 6][1] = sx;
+                red[tid >> 6][2] = sy;
             }
         }
         __syncthreads();
-    }
-    if (tid < 256) {
-        z = wave_sum(z);
-        sx = wave_sum(sx);
-        sy = wave_sum(sy);
-        if ((tid & 63) == 0) {
-            red[tid >> 6][0] = z;
-            red[tid >> 6][1] = sx;
-            red[tid >> 6][2] = sy;
-        }
-    }
-    __syncthreads();
-    if (tid == 0) {
         z = red[0][0] + red[1][0] + red[2][0] + red[3][0];
         sx = red[0][1] + red[1][1] + red[2][1] + red[3][1];
         sy = red[0][2] + red[1][2] + red[2][2] + red[3][2];
+        if (exact || z >= READOUT_Z_MIN) break;  // block-uniform: every thread has read the same four partial sums
+        __syncthreads();
+        float m2 = -INFINITY;
+        for (int i = tid; i < H * W; i += 1024) {
+            const int y = i / W, x = i - y * W;
+            const int px = tx0[x], py = ty0[y];
+            m2 = fmaxf(m2, lerp2(lo, py & 0xFFFF, py >> 16, px & 0xFFFF, px >> 16, tlx[x], tly[y]));
+        }
+        m2 = wave_max(m2);
+        float* redw = &red[0][0];  // 16 waves: one float each of the 32
+        if ((tid & 63) == 0) redw[tid >> 6] = m2;
+        __syncthreads();
+        mx = -INFINITY;
+        for (int i = 0; i < 16; ++i) mx = fmaxf(mx, redw[i]);
+        __syncthreads();
+    }
+    if (tid == 0) {
         traj[((long long)n * 2 + 0) * T + t] = sx / z;
         traj[((long long)n * 2 + 1) * T + t] = sy / z;
         vis[(long long)n * T + t] = s1 / (float)(H * W);
@@ -1630,7 +1685,7 @@ int launch_mask_product(int dtype, const void* up, const float* hyper, float* ma
     const int es = esize_of(dtype);
     const int VT = 128;
     const size_t lds_tile = ((size_t)3 * Cc * 4 + 15) / 16 * 16 + (size_t)VT * Cc * es;
-    if (lds_tile <= 160 * 1024) {
+    if (lds_tile <= LDS_DEVICE_LIMIT) {
         const dim3 grid((unsigned)((vox + VT - 1) / VT), N);
         L4P_WITH_T(dtype, T, {
             auto kern = mask_product_lds_kernel<T, 128>;
@@ -1686,10 +1741,21 @@ int launch_mask_gather(const float* partial, float* masks, int N, int T, int h, 
 
 int launch_track_readout(const float* masks, float* traj, float* vis, float* depth, int N, int T, int h, int w, int H,
                          int W, hipStream_t stream) {
+    if (!masks || !traj || !vis || !depth || N < 1 || T < 1 || h < 1 || w < 1 || H < 1 || W < 1 || (long long)N * T > 0x7FFFFFFFLL) {
+        l4p_set_error("track_readout: needs every pointer and N, T, h, w, H, W >= 1 (N=%d T=%d h=%d w=%d H=%d W=%d)", N, T, h, w, H, W);
+        return L4P_E_INVALID;
+    }
+    // both kernels keep the three low-resolution maps in LDS (+ the 128 static bytes of red[][])
+    const size_t lds_static = 4 * 8 * sizeof(float);
+    const unsigned long long lds_need = (3ull * (unsigned long long)h * w + w + h) * 4 + lds_static;
+    if (lds_need > LDS_DEVICE_LIMIT) {
+        l4p_set_error("track_readout: the %d x %d source maps need %llu bytes of LDS, the device has %zu", h, w, lds_need, LDS_DEVICE_LIMIT);
+        return L4P_E_INVALID;
+    }
     // the 1024-thread form: few (track, frame) workgroups - a rank's query shard of the sharded long video - leave most of the chip idle
     // and the launch is one workgroup's serial walk; with many tracks the 256-thread form fills the chip just as well
     const size_t lds_wide = ((size_t)3 * h * w + w + h + 2 * (W + H) + (size_t)READOUT_RB * W) * 4;
-    if (knob(KNOB_READOUT_WIDE) && W <= 256 && h * w < 65536 && N * T <= 512 && lds_wide <= 160 * 1024) {
+    if (knob(KNOB_READOUT_WIDE) && W <= 256 && h * w < 65536 && N * T <= 512 && lds_wide + lds_static <= LDS_DEVICE_LIMIT) {
         static lds_attr_state attr_wide;
         HIP_TRY(lds_attr_once(attr_wide, track_readout_wide_kernel, (int)lds_wide));
         ProfScope prof(PROF_TRACK, stream, "track_readout wide");

@@ -154,6 +154,60 @@ def mask_product_ref(up, hyper):
 
 
 # ------------------------------------------------------------------------------------------------
+# tracker output tail: gather of the mask up-scaling's partial sums, read-out of the mask logits
+# ------------------------------------------------------------------------------------------------
+# id, (N, T), (h, w), (H, W), wide: whether launch_track_readout takes the 1024-thread form with the knob readout_wide on
+# (W <= 256, N T <= 512 and its LDS request (3 h w + w + h + 2 (W + H) + 32 W) * 4 <= 160 KiB)
+READOUT_CASES = [
+    ("int4_nonsquare", (3, 2), (8, 12), (32, 48), True),     # integer scale, h != w, W < 64: lanes tid >= W inside the one summed wave
+    ("frac_small", (2, 3), (6, 10), (20, 36), True),         # non-integer scales, H < 32: one partial row block
+    ("row_tail", (2, 1), (10, 6), (72, 40), True),           # row blocks 32 + 32 + 8, T = 1
+    ("identity", (1, 2), (7, 5), (7, 5), True),              # lam == 0 everywhere
+    ("wide_W", (1, 2), (8, 72), (16, 288), False),           # W > 256: column form, a second x stride
+    ("many_groups", (33, 16), (6, 10), (20, 36), False),     # N T = 528 > 512
+    ("lds_over", (1, 2), (112, 112), (16, 128), False),      # wide LDS 168 960 B > 160 KiB (column form: 151 424 B); down-sampling in y
+    ("model", (2, 2), (56, 56), (224, 224), True),           # the workload's geometry
+]
+
+# (N, T, h, w, chunks per tap); N T 4 h w voxels per channel: 360, 120, 368 640 (1440 blocks of 256) and 4 262 400 - past the
+# 16 384 * 256 = 4 194 304 the capped grid covers in one trip of its grid-stride loop
+MASK_GATHER_CASES = [(3, 2, 3, 5, 2), (2, 1, 5, 3, 1), (5, 4, 64, 72, 1), (4, 3, 296, 300, 1)]
+
+
+def mask_gather_ref(partial, N, T, h, w, cpt):
+    """partial [4 * cpt][3][M] with M = N T h w (chunk c of tap (dy, dx) is slice (dy * 2 + dx) * cpt + c; row m = ((n T + t) h + y) w + x)
+    -> float32 numpy [N][3][T][2 h][2 w]: out[n][i][t][2 y + dy][2 x + dx] = the float32 sum over the tap's chunks in index order."""
+    p = np.asarray(partial, dtype=np.float32).reshape(2, 2, cpt, 3, N, T, h, w)
+    out = np.zeros((N, 3, T, 2 * h, 2 * w), dtype=np.float32)
+    for dy in range(2):
+        for dx in range(2):
+            acc = np.zeros((3, N, T, h, w), dtype=np.float32)
+            for c in range(cpt):
+                acc = acc + p[dy, dx, c]  # float32 + float32, one rounding per chunk, as the kernel's a += pp[..]
+            out[:, :, :, dy::2, dx::2] = acc.transpose(1, 0, 2, 3, 4)
+    return out
+
+
+def track_readout_ref(masks, H, W, index_dtype=np.float32):
+    """masks [N][3][T][h][w] -> float64 numpy (traj [N][2][T] = (x, y), vis [N][T], depth [N][T]): bilinear resize (align_corners False;
+    the source index formed in ``index_dtype`` by axis_taps: float32 is what ATen and the kernel form for float data, float64 what ATen
+    forms for double data) to H x W; channel 0: softmax over the H W samples with their TRUE maximum as the shift, expectation of the
+    pixel centres (+0.5); channel 1: spatial mean; channel 2: exp(spatial mean)."""
+    m = np.asarray(masks, dtype=np.float64)
+    h, w = m.shape[-2:]
+    y0, y1, ly = (a.numpy() for a in axis_taps(h, H, False, index_dtype))
+    x0, x1, lx = (a.numpy() for a in axis_taps(w, W, False, index_dtype))
+    rows = m[..., y0, :] * (1.0 - ly)[:, None] + m[..., y1, :] * ly[:, None]
+    up = rows[..., x0] * (1.0 - lx) + rows[..., x1] * lx  # [N][3][T][H][W]
+    z = up[:, 0]
+    e = np.exp(z - z.max(axis=(-1, -2), keepdims=True))
+    p = e / e.sum(axis=(-1, -2), keepdims=True)
+    tx = (p.sum(axis=-2) * (np.arange(W) + 0.5)).sum(-1)
+    ty = (p.sum(axis=-1) * (np.arange(H) + 0.5)).sum(-1)
+    return np.stack([tx, ty], axis=1), up[:, 1].mean(axis=(-1, -2)), np.exp(up[:, 2].mean(axis=(-1, -2)))
+
+
+# ------------------------------------------------------------------------------------------------
 # LayerNorm with the tracker's extras
 # ------------------------------------------------------------------------------------------------
 def layernorm_ex_ref(x, g, b, eps, add=None, add_mod=0, act=0):

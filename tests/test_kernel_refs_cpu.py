@@ -102,6 +102,59 @@ def test_mask_product_ref_vs_bmm(C):
             close(R.mask_product_ref(up, hyper), torch.bmm(hyper, up.transpose(1, 2)))
 
 
+@pytest.mark.parametrize("name,NT,lo,hi,wide", R.READOUT_CASES, ids=[c[0] for c in R.READOUT_CASES])
+def test_track_readout_ref_vs_interpolate_softmax_f64(name, NT, lo, hi, wide):
+    """sparse_heads.py:572-589,645-647 in torch's own float64 ops (ATen indexes double data in double: index_dtype = float64), on random
+    logits and on a peaked channel 0 (one source pixel 600 above the rest), where the softmax is near one-hot.  The float32 index the
+    kernel tests use comes from the same axis_taps, checked against float32 F.interpolate above."""
+    (N, T), (h, w), (H, W) = NT, lo, hi
+    N = min(N, 3)  # (many_groups: its geometry, not its 528 groups)
+    masks = torch.stack([rnd((N, T, h, w), 60 + c, 3.0) for c in range(3)], dim=1)
+    peaked = masks.clone()
+    peaked[:, 0] -= 300.0
+    peaked[:, 0, :, h // 2, w // 3] = 300.0
+    xs, ys = torch.arange(W, dtype=torch.float64) + 0.5, torch.arange(H, dtype=torch.float64) + 0.5
+    for m in (masks, peaked):
+        up = F.interpolate(m, size=(T, H, W), mode="trilinear", align_corners=False)
+        p = torch.softmax(up[:, 0].reshape(N, T, H * W), dim=-1).reshape(N, T, H, W)
+        want = torch.stack([(p.sum(2) * xs).sum(-1), (p.sum(3) * ys).sum(-1)], dim=1)
+        traj, vis, depth = (torch.from_numpy(a) for a in R.track_readout_ref(m.numpy(), H, W, np.float64))
+        assert traj.shape == (N, 2, T) and vis.shape == (N, T) and depth.shape == (N, T)
+        close(traj, want)
+        close(vis, up[:, 1].mean((-1, -2)))
+        close(depth, up[:, 2].mean((-1, -2)).exp())
+        # the float32 index moves a weight by a few 1e-8: the estimates move with it, far below the kernel tests' gates
+        t32 = torch.from_numpy(R.track_readout_ref(m.numpy(), H, W)[0])
+        assert (t32 - want).abs().max().item() <= 1e-4
+
+
+def test_track_readout_ref_one_hot_identity_is_the_pixel_centre():
+    m = np.full((1, 3, 1, 7, 5), -1e3)
+    m[0, 0, 0, 4, 1] = 1e3
+    traj, vis, depth = R.track_readout_ref(m, 7, 5)
+    assert traj[0, 0, 0] == 1.5 and traj[0, 1, 0] == 4.5 and vis[0, 0] == -1e3 and depth[0, 0] == 0.0
+
+
+@pytest.mark.parametrize("N,T,h,w,cpt", R.MASK_GATHER_CASES[:2] + [(2, 3, 4, 6, 3)])
+def test_mask_gather_ref_vs_einsum(N, T, h, w, cpt):
+    """The statement of include/l4p_hip.h (row m = ((n T + t) h + y / 2) w + x / 2, tap = (y % 2) * 2 + x % 2) by reshape + einsum.  Integer-valued
+    floats: every sum is exact, so the fixed-order float32 sum and the einsum must agree to the bit."""
+    g = torch.Generator().manual_seed(70)
+    partial = torch.randint(-1000, 1000, (4 * cpt, 3, N * T * h * w), generator=g).float()
+    want = torch.einsum("abcintyx->nityaxb", partial.reshape(2, 2, cpt, 3, N, T, h, w)).reshape(N, 3, T, 2 * h, 2 * w)
+    got = R.mask_gather_ref(partial.numpy(), N, T, h, w, cpt)
+    assert got.dtype == np.float32 and np.array_equal(got, want.numpy())
+    # and element by element from the header's index formula
+    M = N * T * h * w
+    for (n, i, t, y, x) in [(0, 0, 0, 0, 0), (N - 1, 2, T - 1, 2 * h - 1, 2 * w - 1), (N - 1, 1, 0, 1, 2 * w - 2), (0, 2, T - 1, 2 * h - 2, 3)]:
+        m_ = ((n * T + t) * h + y // 2) * w + x // 2
+        tap = (y % 2) * 2 + x % 2
+        s = np.float32(0)
+        for c in range(cpt):
+            s = s + partial.numpy().reshape(-1)[((tap * cpt + c) * 3 + i) * M + m_]
+        assert got[n, i, t, y, x] == s
+
+
 @pytest.mark.parametrize("act", [0, 1])
 @pytest.mark.parametrize("M,C", R.LN_SHAPES)
 def test_layernorm_ex_ref_vs_layer_norm(M, C, act):
