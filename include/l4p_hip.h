@@ -117,6 +117,8 @@ int l4p_stream_destroy(l4p_stream stream);
  *   "epi_generic" (L4P_EPI_GENERIC, default 0): 1 = the generic epilogue instead of the lean ones (l4p_gemm_desc.tuning bit 0)
  *   "gemm_variant" (L4P_GEMM_VARIANT, default 0): 1 = never use the 8-phase kernel, 10 = always, 3 = 128x64 tiles
  *   "gemm_t192"  (L4P_GEMM_T192, default 1): 256 x 192 tiles of the 8-phase kernel where they quantise better on the 256 CUs; 0 = 256 x 256
+ *   "gemm_8p_body" (L4P_GEMM_8P_BODY, default 0): main-loop body of the dense, non-split-K 8-phase kernel: 0 = the launcher's choice per shape,
+ *                1 = two phases of 32 MFMAs per k-tile, 2 = four phases of 16 (bit-identical; profiler tags "8p 2ph" / "8p 4ph")
  * Attention, up-sampling, the encoder:
  *   "attn_persist" (L4P_ATTN_PERSIST, default 1): the persistent form of the 16-bit attention kernel where it applies; 0 = one workgroup per tile
  *   "attn_variant" (L4P_ATTN_VARIANT, default 0): tuning aid: 1 = compiler-scheduled body, 2 = no query split

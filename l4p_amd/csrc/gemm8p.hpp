@@ -20,6 +20,7 @@
 //        RAW: data waited for in phase q is first read in phase q+1        (W1: q=P1',r=P2'; A1: P2'/P3'; A0: P3'/P1''; W0: P4'/P1'')
 //        WAR: a half-tile is re-staged >= 2 phases after its last ds_read  (W1: read P2, staged P1'; A1: P3/P2'; A0: P1/P3; W0: P1/P4)
 //    Past the last k-tile the phases stage zero chunks so the counted waits stay exact.
+//  * dense launches with K >= 512 run the same k-tile as TWO phases of two quadrants (TWOPH, in front of the kernel below).
 #pragma once
 #include "gemm.hpp"
 
@@ -48,9 +49,40 @@ struct Gemm8pCfg {
 // SUBPIX (MODE 1 without split-K): the sub-pixel conv (gemm.hpp, subpix_cells): the k-tile sequence of a tile is the active cells of its
 // sub-position x Cin / 64 channel slices - the staging counters step through those cells, the phases are untouched - and the epilogue is
 // gemm_epilogue_subpixel.
-template <typename T, int MODE, int WR, int WC, bool SPLITK = false, int TM = 8, int TN = 4, bool PERSIST = false, bool SUBPIX = false>
+// TWOPH (MODE 0 without split-K, not persistent; gemm_select.hpp gemm_8p_two_phase, knob gemm_8p_body): the same k-tile as TWO phases of
+// two C quadrants each - 32 MFMAs per barrier pair (24 on the 4 x 6 form) where the body above has 16 (12) - and a steady state whose
+// staging is predicate-free: what the LDS-halo conv gained from (conv3_halo.hpp).  Same LDS layout, buffers, fragments, INFLIGHT:
+//        PA(t): read W0 + W1 + A0 (t) | stage A1(t+1)                   | Q00, Q01
+//        PB(t): read A1 (t)           | stage A0(t+2), W0(t+2), W1(t+2) | Q11, Q10
+//    A phase = [ds_reads, LDS-DMA, vmcnt(INFLIGHT) + lgkmcnt(0)] s_barrier [32 MFMAs at raised priority] s_barrier.  A quadrant keeps
+//    its kk order and every accumulator sees the k-tiles in order: bit-identical to the four-phase body (tests/test_gemm8p_phases_gpu.py).
+//  * issue order of a wave's LDS-DMA: prologue A0 W0 W1 A1 (0), A0 W0 W1 (1); then PA(0): A1(1); PB(0): A0 W0 W1 (2); PA(1): A1(2); ...
+//    Any INFLIGHT = 2 A_PASS + 2 W_PASS consecutive requests of that sequence are one whole k-tile's worth, so behind its own issue
+//      - PA(t)'s vmcnt(INFLIGHT) leaves A1(t+1) and A0 W0 W1 (t+1) in flight: A1(t) - and everything older - has landed;
+//      - PB(t)'s leaves A0 W0 W1 (t+2) and A1(t+1): A0 W0 W1 (t+1) have landed;
+//      - the wait in front of the loop leaves A1(0), A0 W0 W1 (1): A0 W0 W1 (0) have landed.
+//  * hazards.  Barriers numbered per workgroup, the groups one barrier apart: group 0 runs the read/stage segment of PA(t) before
+//    barrier 4t, its MFMAs between 4t and 4t+1, PB(t)'s segment between 4t+1 and 4t+2, its MFMAs between 4t+2 and 4t+3; group 1 runs
+//    each of these one barrier later.  Every segment ends with lgkmcnt(0) BEFORE its barrier: a wave's fragment reads have returned
+//    when it arrives, which is what makes a distance of one barrier enough.
+//        half-tile | waited for (RAW)              | first read                 | last read           | restaged (WAR)
+//        A0 W0 W1  | PB(t-1): g0 < 4t-2, g1 < 4t-1 | PA(t): g0 > 4t-1, g1 > 4t  | PA(t): g0 < 4t,     | PB(t): g0 > 4t+1,
+//        (t)       |                               |                            |        g1 < 4t+1    |        g1 > 4t+2
+//        A1 (t)    | PA(t): g0 < 4t, g1 < 4t+1     | PB(t): g0 > 4t+1, g1 > 4t+2| PB(t): g0 < 4t+2,   | PA(t+1): g0 > 4t+3,
+//                  |                               |                            |        g1 < 4t+3    |          g1 > 4t+4
+//    RAW: the last wave to wait (g1) does so before the barrier after which the first reader (g0) starts.  WAR: the last reader (g1)
+//    has its data before the barrier after which the first writer (g0) issues.  Data waited for in a phase is read in the next one.
+//  * steady state: k-tile pairs whose staged k-tiles (up to t + 3) lie wholly inside K: the per-lane sources are running pointers,
+//    advanced by one k-tile (BK * 2 bytes) per k-tile - no compare, select or 64-bit multiply-add.  The k-tiles that stage the K-tail
+//    or past the end are peeled behind that loop and predicate every chunk (zero chunks: the counted waits stay exact).
+//    Emitted steady-state loop (bf16, two k-tiles per trip; the four-phase loop in brackets): 8 x 4 form 30 VALU + 53 scalar for 128
+//    MFMAs = 0.23 + 0.41 per MFMA [0.77 + 0.73]; 4 x 6 form 28 + 48 for 96 = 0.29 + 0.50 [1.05 + 0.98].  The staging costs one
+//    v_lshl_add_u64 (pointer + the loop's scalar k offset) and one M0 write per LDS-DMA; no v_cmp / v_cndmask is left [38 / 41].
+template <typename T, int MODE, int WR, int WC, bool SPLITK = false, int TM = 8, int TN = 4, bool PERSIST = false, bool SUBPIX = false,
+          bool TWOPH = false>
 __global__ __launch_bounds__(512) void gemm8p_kernel(const GemmParams p) {
     static_assert(!PERSIST || (MODE == 0 && !SPLITK), "persistent form: dense GEMM without split-K");
+    static_assert(!TWOPH || (MODE == 0 && !SPLITK && !PERSIST), "two-phase body: dense GEMM without split-K, one tile per workgroup");
     static_assert(!SUBPIX || (MODE == 1 && !SPLITK && !PERSIST), "sub-pixel conv: the conv form without split-K");
     static_assert(WR * WC == 8 && (WC == 2 || WC == 4), "8 waves");
     static_assert(TM % 2 == 0 && TN % 2 == 0 && (WR * TM) % 8 == 0, "half tiles; A half-tile = whole 64-row staging passes");
@@ -283,8 +315,7 @@ __global__ __launch_bounds__(512) void gemm8p_kernel(const GemmParams p) {
 #pragma unroll
             for (int kk = 0; kk < 2; ++kk) wb[h][jj][kk] = *(const vec8<T>*)(base + w_off[kk] + jj * 512);
     };
-    auto quadrant = [&](int qa, int qw) {
-        __builtin_amdgcn_s_setprio(1);
+    auto quadrant_mfma = [&](int qa, int qw) {
 #pragma unroll
         for (int kk = 0; kk < 2; ++kk)
 #pragma unroll
@@ -293,6 +324,10 @@ __global__ __launch_bounds__(512) void gemm8p_kernel(const GemmParams p) {
                 for (int jj = 0; jj < TN / 2; ++jj)
                     acc[qa * (TM / 2) + ii][qw * (TN / 2) + jj] =
                         mma16(wb[qw][jj][kk], xa[ii][kk], acc[qa * (TM / 2) + ii][qw * (TN / 2) + jj]);
+    };
+    auto quadrant = [&](int qa, int qw) {
+        __builtin_amdgcn_s_setprio(1);
+        quadrant_mfma(qa, qw);
         __builtin_amdgcn_s_setprio(0);
     };
     // end of a phase's read/stage segment: counted wait for the half-tile staged four phases ago, then the barrier
@@ -315,8 +350,54 @@ __global__ __launch_bounds__(512) void gemm8p_kernel(const GemmParams p) {
         stage_a(1, 0, 0);
         stage_a(0, 1, 1);
         stage_w(0, 1, 1);
+        if constexpr (TWOPH) stage_w(1, 1, 1);  // (two-phase body: ... and W1 of k-tile 1)
     };
     prologue_stage();
+
+    // ---- two-phase body: the sources become running pointers - A1 stands at k-tile 1, A0 / W0 / W1 at k-tile 2, each stage call moves
+    //      its half-tile's pointers on by one k-tile.  Filler rows of W (never read) keep the zero chunk: their step is 0. ----
+    constexpr bool W_FILL = (WC * CH) % 64 != 0;  // the last W pass has filler rows
+    int w_step_last = BK * 2;
+    if constexpr (TWOPH) {
+#pragma unroll
+        for (int i = 0; i < A_PASS; ++i) {
+            a_src[i][0] += 2 * BK * 2;
+            a_src[i][1] += BK * 2;
+        }
+#pragma unroll
+        for (int i = 0; i < W_PASS; ++i)
+#pragma unroll
+            for (int h = 0; h < 2; ++h) w_src[i][h] = w_src[i][h] != nullptr ? w_src[i][h] + 2 * BK * 2 : zero;
+        if (W_FILL && srow + 64 * (W_PASS - 1) >= WC * CH) w_step_last = 0;
+    }
+    // stage the half-tile of k-tile kt from the running pointers and move them on.  TAIL: every chunk predicated on lying inside K
+    auto stage_a2 = [&](auto tail_c, int h, int kt, int buf) {
+#pragma unroll
+        for (int i = 0; i < A_PASS; ++i) {
+            const char* src = a_src[i][h];
+            if constexpr (decltype(tail_c)::value) src = kt * BK + cs_a * 8 < p.K ? src : zero;
+            __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(smem + buf * BUF + h * A_HALF + (i * 512 + wave * 64) * 16), 16,
+                                             0, 0);
+            a_src[i][h] += BK * 2;
+        }
+    };
+    auto stage_w2 = [&](auto tail_c, int h, int kt, int buf) {
+#pragma unroll
+        for (int i = 0; i < W_PASS; ++i) {
+            const char* src = w_src[i][h];
+            if constexpr (decltype(tail_c)::value) src = kt * BK + cs_w[i] * 8 < p.K ? src : zero;
+            __builtin_amdgcn_global_load_lds((gptr_t)src,
+                                             (lptr_t)(smem + buf * BUF + 2 * A_HALF + h * W_HALF + (i * 512 + wave * 64) * 16), 16, 0, 0);
+            w_src[i][h] += (W_FILL && i == W_PASS - 1) ? w_step_last : BK * 2;
+        }
+    };
+    // end of a read/stage segment of the two-phase body: the counted wait, and this wave's fragment reads have returned
+    auto seg_end2 = [&]() {
+        __builtin_amdgcn_sched_barrier(0);  // (address arithmetic of later phases stays in front of the wait, not between it and the barrier)
+        asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(INFLIGHT) : "memory");
+        __builtin_amdgcn_s_barrier();
+        __builtin_amdgcn_sched_barrier(0);
+    };
     for (;;) {  // tile loop (one pass unless PERSIST)
     // (past a seam the epilogue's stores are younger than the prologue's requests and memory operations retire in order: the
     //  counted wait still means "at most the four youngest half-tile stages are outstanding")
@@ -357,9 +438,50 @@ __global__ __launch_bounds__(512) void gemm8p_kernel(const GemmParams p) {
         quadrant(1, 0);
         phase_end();
     };
-    for (int t = 0; t < nk; t += 2) {
-        ktile(t, std::integral_constant<int, 0>{});
-        if (t + 1 < nk) ktile(t + 1, std::integral_constant<int, 1>{});
+    auto ktile2 = [&](int t, auto cur_c, auto tail_c) {
+        constexpr int cur = decltype(cur_c)::value, nxt = cur ^ 1;
+        // PA
+        read_w(0, cur);
+        read_w(1, cur);
+        read_a(0, cur);
+        stage_a2(tail_c, 1, t + 1, nxt);
+        seg_end2();
+        __builtin_amdgcn_s_setprio(1);
+        quadrant_mfma(0, 0);
+        quadrant_mfma(0, 1);
+        __builtin_amdgcn_s_setprio(0);
+        phase_end();
+        // PB
+        read_a(1, cur);
+        stage_a2(tail_c, 0, t + 2, cur);
+        stage_w2(tail_c, 0, t + 2, cur);
+        stage_w2(tail_c, 1, t + 2, cur);
+        seg_end2();
+        __builtin_amdgcn_s_setprio(1);
+        quadrant_mfma(1, 1);
+        quadrant_mfma(1, 0);
+        __builtin_amdgcn_s_setprio(0);
+        phase_end();
+    };
+    if constexpr (TWOPH) {
+        const std::integral_constant<int, 0> b0{};
+        const std::integral_constant<int, 1> b1{};
+        int t = 0;
+        // steady state: pairs of k-tiles that stage whole k-tiles only (k-tile t + 1 stages k-tile t + 3)
+        for (const int nfull = p.K / BK; t + 3 < nfull; t += 2) {
+            ktile2(t, b0, std::false_type{});
+            ktile2(t + 1, b1, std::false_type{});
+        }
+        // the k-tiles that stage the K-tail or zero chunks past the end
+        for (; t < nk; t += 2) {
+            ktile2(t, b0, std::true_type{});
+            if (t + 1 < nk) ktile2(t + 1, b1, std::true_type{});
+        }
+    } else {
+        for (int t = 0; t < nk; t += 2) {
+            ktile(t, std::integral_constant<int, 0>{});
+            if (t + 1 < nk) ktile(t + 1, std::integral_constant<int, 1>{});
+        }
     }
     if (grp == 0) __builtin_amdgcn_s_barrier();  // pairs with the trailing barrier of the delayed group
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // (only zero-chunk dummies are still in flight)

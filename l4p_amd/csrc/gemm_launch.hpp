@@ -116,13 +116,13 @@ static int launch_subpixel(const GemmParams& p, hipStream_t stream, GemmForm for
 }
 
 // 8-phase deep-pipelined kernel (gemm8p.hpp), 16-bit only, no fused input ReLU
-template <typename T, int MODE, int WR, int WC, bool SPLITK = false, int TM = 8, int TN = 4>
+template <typename T, int MODE, int WR, int WC, bool SPLITK = false, int TM = 8, int TN = 4, bool TWOPH = false>
 static int launch_8p(const GemmParams& p, hipStream_t stream, GemmForm form) {
     typedef Gemm8pCfg<WR, WC, TM, TN> Cfg;
     const int ntm = (p.M + Cfg::BM - 1) / Cfg::BM, ntn = (p.N + Cfg::BN - 1) / Cfg::BN;
     const int nsplit = SPLITK ? p.splitk : 1;
     const size_t lds = Cfg::LDS_BYTES;
-    auto kern = gemm8p_kernel<T, MODE, WR, WC, SPLITK, TM, TN, false>;
+    auto kern = gemm8p_kernel<T, MODE, WR, WC, SPLITK, TM, TN, false, false, TWOPH>;
     static lds_attr_state attr_done;
     HIP_TRY(lds_attr_once(attr_done, kern, (int)lds));
     ProfScope prof = gemm_prof(MODE == 0 ? PROF_GEMM : PROF_CONV3D, stream, p, p.K, form, nsplit);
@@ -199,6 +199,7 @@ static GemmKnobs gemm_knobs() {
 #else
     k.probe_kernels = 0;
 #endif
+    k.gemm_8p_body = knob(KNOB_GEMM_8P_BODY);
     return k;
 }
 
@@ -221,8 +222,16 @@ static int launch_form(GemmForm form, const GemmParams& p, hipStream_t stream) {
         switch (form) {
             case GEMM_WGRP_64x64_DEEP: return launch_cfg<T, 64, 64, 0, true, 4, true>(p, stream, form);
             case GEMM_WGRP_128x64_DEEP: return launch_cfg<T, 128, 64, 0, true, 4, true>(p, stream, form);
-            case GEMM_8P_256x256: return launch_8p<T, 0, 2, 4>(p, stream, form);
-            case GEMM_8P_256x192: return launch_8p<T, 0, 4, 2, false, 4, 6>(p, stream, form);
+            // (the plain enumerators: the body gemm_8p_two_phase names for the shape; _2PH / _4PH: knob gemm_8p_body)
+            case GEMM_8P_256x256:
+                return gemm_8p_two_phase(p, form) ? launch_8p<T, 0, 2, 4, false, 8, 4, true>(p, stream, form) : launch_8p<T, 0, 2, 4>(p, stream, form);
+            case GEMM_8P_256x192:
+                return gemm_8p_two_phase(p, form) ? launch_8p<T, 0, 4, 2, false, 4, 6, true>(p, stream, form)
+                                                  : launch_8p<T, 0, 4, 2, false, 4, 6>(p, stream, form);
+            case GEMM_8P_2PH_256x256: return launch_8p<T, 0, 2, 4, false, 8, 4, true>(p, stream, form);
+            case GEMM_8P_2PH_256x192: return launch_8p<T, 0, 4, 2, false, 4, 6, true>(p, stream, form);
+            case GEMM_8P_4PH_256x256: return launch_8p<T, 0, 2, 4>(p, stream, form);
+            case GEMM_8P_4PH_256x192: return launch_8p<T, 0, 4, 2, false, 4, 6>(p, stream, form);
             case GEMM_8P_SK_256x256: return launch_8p<T, 0, 2, 4, true>(p, stream, form);
             case GEMM_8P_SK_256x192: return launch_8p<T, 0, 4, 2, true, 4, 6>(p, stream, form);
             case GEMM_8P_CONV: return launch_8p<T, 1, 2, 4>(p, stream, form);

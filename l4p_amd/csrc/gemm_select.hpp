@@ -51,6 +51,12 @@ enum GemmForm {
     // sub-pixel conv (l4p_conv3d_subpixel): staged 128x128, and 8-phase (16-bit)
     GEMM_SUBPIX_STAGED,
     GEMM_SUBPIX_8P,
+    // 8-phase kernel, dense without split-K, with its main-loop body forced (knob gemm_8p_body = 1 / 2: A/B and parity aids; the plain
+    // enumerators above take the body gemm_8p_two_phase names)
+    GEMM_8P_2PH_256x256,
+    GEMM_8P_2PH_256x192,
+    GEMM_8P_4PH_256x256,
+    GEMM_8P_4PH_256x192,
     GEMM_FORM_NUM
 };
 
@@ -61,6 +67,7 @@ enum GemmGroupForm { GEMM_GROUP_INVALID = 0, GEMM_GROUP_SKINNY, GEMM_GROUP_DEEP,
 struct GemmKnobs {
     int gemm_variant, conv_halo, gemm_skinny, skinny_max_m, gemm_deep, gemm_group, track_deep, gemm_t192, gemm_4w;
     int probe_kernels;  // the build has the measured-and-not-adopted kernels (PROBES=1)
+    int gemm_8p_body;   // main-loop body of the dense 8-phase forms: 0 = gemm_8p_two_phase decides, 1 = two phases per k-tile, 2 = four
 };
 
 // ---- the forms' names: the tail of the profiler tag after "M%d N%d K%d epi%d act%d " (the tests match these byte for byte) ----
@@ -95,6 +102,10 @@ inline const char* gemm_form_tag(GemmForm form, int nsplit, char (&buf)[GEMM_TAG
         case GEMM_4W: return "4w t256x128";
         case GEMM_SUBPIX_STAGED: return "subpix t128x128";
         case GEMM_SUBPIX_8P: return "subpix 8p t256x256";
+        case GEMM_8P_2PH_256x256: return "8p 2ph t256x256";
+        case GEMM_8P_2PH_256x192: return "8p 2ph t256x192";
+        case GEMM_8P_4PH_256x256: return "8p 4ph t256x256";
+        case GEMM_8P_4PH_256x192: return "8p 4ph t256x192";
         default: return "invalid";
     }
     snprintf(buf, sizeof buf, "%ssk%d%s", head, nsplit, tail);
@@ -157,6 +168,14 @@ inline bool epilogue_is_lean_8p(const l4p_gemm_desc& p) {
     if (p.epi == L4P_EPI_QKV) return !p.res1 && p.act == L4P_ACT_NONE && p.c_gr == 0;
     if (p.epi == L4P_EPI_CONVT) return !p.res1 && p.act == L4P_ACT_NONE && p.out_T && !p.out_f32 && !p.out_relu_T;
     return dense_epilogue_is_lean(p);
+}
+
+// Main-loop body of a dense, non-split-K 8-phase launch (gemm8p.hpp; form: GEMM_8P_256x256 or GEMM_8P_256x192): true = two phases of
+// 32 / 24 MFMAs per k-tile with predicate-free steady-state staging, false = four phases of 16 / 12.  Same sums in the same order.
+// Rule: the two-phase body from 8 whole k-tiles on (K >= 512); below that most k-tiles of a tile run its peeled, predicated form
+// (measured on c3, same call: K = 1408 / 6144 shapes 2.0 - 10.2 % faster on it, the mask product, K = 352, 2.8 % slower).
+inline bool gemm_8p_two_phase(const l4p_gemm_desc& p, GemmForm form) {
+    return (form == GEMM_8P_256x256 || form == GEMM_8P_256x192) && p.K >= 8 * 64;
 }
 
 // The tile of the LDS-halo conv, host side (the launcher asserts it equal to conv3_halo.hpp's ConvHaloCfg<WR, WC>)
@@ -302,7 +321,11 @@ inline GemmForm gemm_select(int mode, int esize, const l4p_gemm_desc& p, const G
                 // (the batch-4 encoder: out projection / MLP-out 192 tiles -> 256, QKV 576 -> 768; L4P_GEMM_T192=0: A/B aid)
                 const long long n192 = gemm_tiles(p, 256, 192);
                 const long long c256 = (t8 + 255) / 256 * 65536, c192 = (n192 + 255) / 256 * 49152;
-                return k.gemm_t192 && c192 < c256 && epilogue_is_lean_8p(p) ? GEMM_8P_256x192 : GEMM_8P_256x256;
+                const bool t192 = k.gemm_t192 && c192 < c256 && epilogue_is_lean_8p(p);
+                // knob gemm_8p_body: 1 / 2 force the two-phase / four-phase main loop (bit-identical) and say so in the tag
+                if (k.gemm_8p_body == 1) return t192 ? GEMM_8P_2PH_256x192 : GEMM_8P_2PH_256x256;
+                if (k.gemm_8p_body == 2) return t192 ? GEMM_8P_4PH_256x192 : GEMM_8P_4PH_256x256;
+                return t192 ? GEMM_8P_256x192 : GEMM_8P_256x256;
             }
             if (use8 && mode == 1 && p.Cin % 64 == 0) return GEMM_8P_CONV;
         }

@@ -43,6 +43,7 @@ const KnobDef kKnobs[KNOB_NUM] = {{"conv_halo", "L4P_CONV_HALO", 1}, {"gemm_4w",
                                    {"epi_generic", "L4P_EPI_GENERIC", 0},
                                    {"gemm_variant", "L4P_GEMM_VARIANT", 0},
                                    {"gemm_t192", "L4P_GEMM_T192", 1},
+                                   {"gemm_8p_body", "L4P_GEMM_8P_BODY", 0},
                                    {"attn_persist", "L4P_ATTN_PERSIST", 1},
                                    {"attn_variant", "L4P_ATTN_VARIANT", 0},
                                    {"ups_ipt", "L4P_UPS_IPT", 2},

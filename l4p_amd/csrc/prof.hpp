@@ -29,6 +29,7 @@ enum Knob {
     KNOB_TRACK_FOLD_PAIR, KNOB_TRACK_DELTA_KERNEL,
     // the GEMM launchers (gemm_select.hpp / gemm_launch.hpp)
     KNOB_GEMM_PERSIST, KNOB_SKINNY_MAX_M, KNOB_GEMM_DEEP, KNOB_GEMM_GROUP, KNOB_EPI_GENERIC, KNOB_GEMM_VARIANT, KNOB_GEMM_T192,
+    KNOB_GEMM_8P_BODY,
     // attention.hip, dpt_ops.hip, api.hip
     KNOB_ATTN_PERSIST, KNOB_ATTN_VARIANT, KNOB_UPS_IPT, KNOB_UPS_NT, KNOB_FC2_SPLITK8, KNOB_ENC_DEFER_RES, KNOB_ENC_SK_IN_LN,
     // api_dpt.hip
