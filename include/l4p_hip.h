@@ -595,7 +595,13 @@ int l4p_metric_tracks(l4p_stream stream, const float* traj_est, const float* tra
  * |s R c_est + t - c_gt|; with the estimate's translations multiplied by s and E = inv(inv(G_i) G_i+1) (inv(P_i) P_i+1) for
  * consecutive frames: out[1] = rpe_trans = RMSE of |trans(E)|, out[2] = rpe_rot = RMSE in degrees of
  * atan2(0.5 |(E32 - E23, E13 - E31, E21 - E12)|, 0.5 (trace - 1)); out[3] = s, out[4..6] = the three sums of squares, out[7] = T.
- * T >= 3. */
+ * T >= 3.
+ * Degenerate centres (the closed form of csrc/umeyama_moments.hpp, shared with l4p_similarity_ransac; ms, md = the means of the
+ * estimated and the gt centres, var_s = the variance of the estimated ones, cov = their cross-covariance): R is a proper rotation
+ * (R R^T = I, det R = +1) whatever the rank of cov - collinear centres leave the rotation about their line free, and it is fixed by
+ * completing the left singular vectors from the right ones: R = I when the gt line is the estimated line in the same sense (to
+ * rounding, and R stays near I as one line turns away from the other); cov = 0 gives R = I.  var_s = 0 (a
+ * static estimate) gives s = 1 and t = md - R ms; cov = 0 with var_s > 0 (a static gt) gives s = 0, hence t = md.  All finite. */
 int l4p_metric_cameras(l4p_stream stream, const float* pose_est, const float* extr_gt, int B, int T, double* out);
 
 /* ------------------------------------------------------------------------------------------------

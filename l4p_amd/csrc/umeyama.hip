@@ -2,7 +2,10 @@
 // overlap depth/pose pairs -> sampled world-space point maps -> RANSAC similarity (Umeyama) -> apply.
 // The reference does this on the CPU with numpy + skimage.measure.ransac (randomised, unpinned version);
 // this is a deterministic counter-based-RNG re-statement of the same estimator, validated against synthetic
-// ground truth (tests/test_umeyama_gpu.py), not against the reference ("parity unpinned").
+// ground truth (tests/test_umeyama_gpu.py: one smooth scene through the aligner; tests/test_similarity_edges_gpu.py: planted
+// similarities at small and ragged n, one trial, planar / mirrored / repeated samples, the refusals, the apply kernels; the closed
+// form itself against a float64 SVD on degenerate clouds in tests/test_umeyama_moments_cpu.py), not against the reference
+// ("parity unpinned").
 #include "common.hpp"
 #include "unproject.hpp"
 #include "umeyama_moments.hpp"

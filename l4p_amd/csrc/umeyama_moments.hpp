@@ -1,13 +1,21 @@
 // Closed-form similarity (Umeyama) from accumulated moments, shared by the seam alignment (umeyama.hip, float model) and the
 // camera metrics (metrics.hip, double model): the code is one template, so both round their f64 arithmetic alike.
+// Plain C++ apart from the __device__ mark (fabs, sqrt and fmax are all it calls), so a host compiler takes it too:
+// tests/umeyama_moments_main.cpp runs it on the CPU against a float64 SVD (tests/test_umeyama_moments_cpu.py).
 #pragma once
+#if defined(__HIPCC__)
 #include "common.hpp"
+#define UMEYAMA_FN __device__
+#else
+#include <math.h>
+#define UMEYAMA_FN
+#endif
 
 // -------------------------------------------------------------------------------------------------
 // Umeyama similarity from accumulated moments (skimage.transform._geometric._umeyama):
 // dst ~ s R src + t.  sums: n, mean_s[3], mean_d[3], cov[3][3] = E[(d-md)(s-ms)^T], var_s.
 // -------------------------------------------------------------------------------------------------
-static __device__ void jacobi3(double A[3][3], double V[3][3]) {
+static UMEYAMA_FN void jacobi3(double A[3][3], double V[3][3]) {
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) V[i][j] = i == j;
     for (int sweep = 0; sweep < 30; ++sweep) {
@@ -39,7 +47,7 @@ static __device__ void jacobi3(double A[3][3], double V[3][3]) {
 
 // model: [0..8] = s*R row-major, [9..11] = t, [12] = s
 template <typename OutT>
-__device__ void umeyama_from_moments(const double ms[3], const double md[3], const double cov[3][3], double var_s,
+UMEYAMA_FN void umeyama_from_moments(const double ms[3], const double md[3], const double cov[3][3], double var_s,
                                      OutT* model) {
     double AtA[3][3], V[3][3];
     for (int i = 0; i < 3; ++i)
@@ -67,10 +75,35 @@ __device__ void umeyama_from_moments(const double ms[3], const double md[3], con
     }
     const double s1 = sqrt(u1[0] * u1[0] + u1[1] * u1[1] + u1[2] * u1[2]);
     for (int i = 0; i < 3; ++i) u1[i] /= fmax(s1, 1e-300);
+    // Rank-deficient cov (a full-rank one takes neither branch below, and nothing it computes has moved): R is a proper rotation all
+    // the same, completed from the orthonormal v's.  cov = 0 (a static dst or src), or so small that the floor above left u1 short
+    // of a unit vector: u1 = v1, hence u2 = v2 below and R = I.
+    if (!(s1 >= 1e-300))
+        for (int i = 0; i < 3; ++i) u1[i] = v1[i];
     const double dp = u1[0] * u2[0] + u1[1] * u2[1] + u1[2] * u2[2];
     for (int i = 0; i < 3; ++i) u2[i] -= dp * u1[i];
-    const double s2 = sqrt(u2[0] * u2[0] + u2[1] * u2[1] + u2[2] * u2[2]);
+    double s2 = sqrt(u2[0] * u2[0] + u2[1] * u2[1] + u2[2] * u2[2]);
     for (int i = 0; i < 3; ++i) u2[i] /= fmax(s2, 1e-300);
+    // u2 did not survive the orthogonalisation: it is exactly zero (collinear centres along a coordinate axis: two rows or columns
+    // of cov are zero and cov v2 - dp u1 cancels exactly, which left R = u1 v1^T with det 0), or it is rounding noise.  The three
+    // products and two sums of a row of cov v2 round by up to 3 eps |cov row| <= 3 eps sigma1 each, 3 sqrt(3) eps sigma1 over the
+    // three rows, and v2 itself carries some eps of v1 out of the Jacobi sweeps, which cov turns into as much again: below
+    // 16 eps sigma1 the direction of what is left says nothing about the data, and taking it for zero moves s by 16 eps at most.
+    // Rank 1 leaves the rotation about u1 free; it is fixed by sending v2 to its own projection off u1 while at least sqrt(1/2) of
+    // it stands off u1, and v3 otherwise (|u1.v2|^2 + |u1.v3|^2 <= 1, so then at least sqrt(1/2) of v3 does).  With u1 = v1 this is
+    // u2 = v2, u3 = v3 and R = I, and R moves continuously with u1 around there (a choice by the smaller of the two products would
+    // flip between v2 and v3 on their rounding).
+    if (!(s2 > 16.0 * 2.220446049250313e-16 * s1)) {
+        const double d2 = u1[0] * v2[0] + u1[1] * v2[1] + u1[2] * v2[2], d3 = u1[0] * v3[0] + u1[1] * v3[1] + u1[2] * v3[2];
+        const bool keep2 = fabs(d2) <= 0.7071067811865476;
+        const double* w = keep2 ? v2 : v3;
+        const double dw = keep2 ? d2 : d3;
+        for (int i = 0; i < 3; ++i) u2[i] = w[i] - dw * u1[i];
+        const double nw = sqrt(u2[0] * u2[0] + u2[1] * u2[1] + u2[2] * u2[2]);
+        for (int i = 0; i < 3; ++i) u2[i] /= nw;
+        s2 = 0;  // u2^T cov v2 of the completed u2: what the scale that fits this R best takes for sigma2
+        for (int i = 0; i < 3; ++i) s2 += u2[i] * (cov[i][0] * v2[0] + cov[i][1] * v2[1] + cov[i][2] * v2[2]);
+    }
     u3[0] = u1[1] * u2[2] - u1[2] * u2[1];
     u3[1] = u1[2] * u2[0] - u1[0] * u2[2];
     u3[2] = u1[0] * u2[1] - u1[1] * u2[0];

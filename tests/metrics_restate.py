@@ -129,7 +129,10 @@ def tracks(traj_est, traj_gt, vis_logit, vis_gt, valid, queries, hw):
 
 
 def umeyama(src, dst):
-    """Closed-form similarity dst ~ s R src + t (Umeyama 1991) in float64 with np.linalg.svd; src, dst [T, 3]."""
+    """Closed-form similarity dst ~ s R src + t (Umeyama 1991) in float64 with np.linalg.svd; src, dst [T, 3].  The reflection is
+    fixed on the last singular value (det(U) det(Vt) < 0 -> -sigma3), so R is a proper rotation at every rank of cov; where it is
+    not unique (rank < 2) it is whichever the SVD returns.  The degenerate contracts of include/l4p_hip.h (l4p_metric_cameras):
+    cov = 0 -> R = I (and s = 0 when var > 0); var = 0 (a static src, hence cov = 0) -> s = 1, R = I, t = md - ms."""
     src, dst = np.asarray(src, np.float64), np.asarray(dst, np.float64)
     ms, md = src.mean(0), dst.mean(0)
     xs, xd = src - ms, dst - md
@@ -139,8 +142,8 @@ def umeyama(src, dst):
     S = np.eye(3)
     if np.linalg.det(U) * np.linalg.det(Vt) < 0:
         S[2, 2] = -1.0
-    R = U @ S @ Vt
-    s = float(np.trace(np.diag(D) @ S) / var)
+    R = U @ S @ Vt if D[0] > 0 else np.eye(3)
+    s = float(np.trace(np.diag(D) @ S) / var) if var > 0 else 1.0
     return s, R, md - s * R @ ms, cov
 
 

@@ -1,7 +1,10 @@
 """GPU: joint depth+pose seam alignment (row a11).  The reference step is skimage RANSAC on the CPU (randomised,
 unpinned) => validated against SYNTHETIC GROUND TRUTH: a known similarity (s, R, t) between two windows'
 overlap must be recovered (1e-3 relative) with 20 % gross outliers present, and applying it must map the
-current window onto the stitched buffer."""
+current window onto the stitched buffer.  This is the friendly case, through the aligner: one smooth scene, n ~ 15 000, small
+rotations.  The estimator's edges (small and ragged n, one trial, planar / mirrored clouds, repeated sample points, no inliers, the
+refusals) are in tests/test_similarity_edges_gpu.py, and its closed form against a float64 SVD on planar, collinear, static and
+ill-conditioned clouds in tests/test_umeyama_moments_cpu.py."""
 import math
 
 import pytest
