@@ -43,7 +43,9 @@ typedef void* l4p_stream; /* hipStream_t */
 typedef struct l4p_engine l4p_engine;
 
 const char* l4p_last_error(void);
-int l4p_abi_version(void); /* 18: the L4PDataset base class (l4p_gt_dense_clip, l4p_gt_query_select, l4p_gt_tracks_clip);
+int l4p_abi_version(void); /* 19: 3D-track metrics, inverse-depth alignment and log-space depth errors (l4p_metric_tracks3d,
+                              * l4p_metric_tracks3d_ws_bytes, l4p_metric_depth_full, l4p_metric_depth_full_ws_bytes);
+                              * 18: the L4PDataset base class (l4p_gt_dense_clip, l4p_gt_query_select, l4p_gt_tracks_clip);
                               * 17: evaluation metrics (l4p_metric_ws_bytes, l4p_metric_depth, l4p_metric_flow, l4p_metric_mask,
                               * l4p_metric_tracks, l4p_metric_cameras, l4p_select_median_dev);
                               * 16: the free-viewpoint 4D renderer (l4p_view_splat, l4p_view_mesh, l4p_view_resolve);
@@ -564,9 +566,32 @@ size_t l4p_metric_ws_bytes(int B, long long n, int mode);
  * Then a = min(max(s * est + t, dmin), dmax) (multiply, then add, unfused); a NaN alignment scores no element.  Per clip
  * out[0..5] = c, sum |a - gt| / gt, sum (a - gt) * (a - gt), the counts of max(a / gt, gt / a) < 1.25f, 1.5625f, 1.953125f;
  * out[6..10] = abs_rel, rmse (the f64 square root of the mean), delta1, delta2, delta3; out[11], out[12] = s, t.
- * 0 < dmin < dmax.  Inverse-depth alignment and log-space errors are not provided. */
+ * 0 < dmin < dmax.  Inverse-depth alignment and log-space errors: l4p_metric_depth_full below. */
 int l4p_metric_depth(l4p_stream stream, const float* est, const float* gt, const float* valid, int B, long long n, int mode,
                      float dmin, float dmax, void* ws, size_t ws_bytes, double* out);
+/* Depth with every alignment and the log-space errors: the arguments of l4p_metric_depth, out [B][L4P_METRIC_DEPTH_FULL_OUT].
+ * Element validity, dmin / dmax and the alignments L4P_DEPTH_ALIGN_NONE / _MEDIAN / _LSTSQ with their aligned value a are those of
+ * l4p_metric_depth, and out[0..12] are its columns bit for bit.  The fourth alignment is scale and shift in inverse depth:
+ *   L4P_DEPTH_ALIGN_LSTSQ_INV  x = 1.f / est, y = 1.f / gt; (s, t) = argmin over the valid elements of sum (s x + t - y)^2: the sums
+ *                              in f64 from the f32 x and y, the 2 x 2 normal equations solved in f64, s and t rounded to f32; NaN
+ *                              when c < 2 or the determinant is <= 0.  Aligned value: p = s * x + t (multiply, then add, unfused),
+ *                              pc = fminf(fmaxf(p, 1.f / dmax), 1.f / dmin), a = fminf(fmaxf(1.f / pc, dmin), dmax).
+ * A NaN alignment scores no element.  Errors of a scored element: d = a - gt in f32, and the log error in f64,
+ * l = log((double)a) - log((double)gt) (an f32 logf would tie the result to one math library's last bit).  Per clip
+ *   out[0..12]   as l4p_metric_depth: c, two sums, three delta counts, abs_rel, rmse, delta1..3, s, t;
+ *   out[13..16]  sum (d * d) / gt (f32 terms), sum l, sum l * l, sum |l|  (f64 sums in a fixed order);
+ *   out[17]      sq_rel = out[13] / c;
+ *   out[18]      rmse_log = sqrt(out[15] / c);
+ *   out[19]      log10 = (out[16] / c) / ln 10;
+ *   out[20]      silog = 100 sqrt(max(out[15] / c - (out[14] / c)^2, 0));
+ *   out[21..23]  NaN (reserved).
+ * out[17..20] are NaN when c = 0.  The workspace is l4p_metric_depth_full_ws_bytes(B, n, align) bytes (0 for arguments the entry
+ * refuses). */
+#define L4P_DEPTH_ALIGN_LSTSQ_INV 3
+#define L4P_METRIC_DEPTH_FULL_OUT 24
+size_t l4p_metric_depth_full_ws_bytes(int B, long long n, int align);
+int l4p_metric_depth_full(l4p_stream stream, const float* est, const float* gt, const float* valid, int B, long long n, int align,
+                          float dmin, float dmax, void* ws, size_t ws_bytes, double* out);
 /* Optical flow: est, gt, valid [B][2][n].  An element is valid when both valid channels are > 0.5 and both gt channels are finite;
  * epe = sqrtf(du * du + dv * dv).  out[0..4] = c, sum epe, the counts of epe < 1, 3, 5; out[5..8] = epe (mean), 1px, 3px, 5px (the
  * shares below the threshold). */
@@ -589,6 +614,41 @@ int l4p_metric_mask(l4p_stream stream, const float* logit, const float* gt, cons
 int l4p_metric_tracks(l4p_stream stream, const float* traj_est, const float* traj_gt, const float* vis_logit,
                       const unsigned char* vis_gt, const unsigned char* valid, const float* queries, int B, int N, int T, int H, int W,
                       unsigned long long* counts, double* out);
+/* 3D tracks, the TAP-Vid measures on camera-space points with depth-adaptive thresholds: traj_est, traj_gt [B][N][2][T] and
+ * depth_est, depth_gt [B][N][T] (track_2d_depth_est_bn1t / track_2d_depth_bn1t: (x, y, z) of frame t), vis_logit [B][N][T], vis_gt
+ * and valid [B][N][T] bytes (valid may be NULL), queries [B][N][3], intrinsics [B][4][4][T] (intrinsics_b44t in the pixel units of
+ * the clip; only fx = K[0][0][t], fy = K[1][1][t], cx = K[0][2][t], cy = K[1][2][t] are read).  All f32, one rounding per operation:
+ *   unprojection (unproject_2d_track_to_3d, geometry_utils.py:69-78): X = ((x - cx) * z) / fx, Y = ((y - cy) * z) / fy, Z = z;
+ *     G from the gt, E from the estimate WITH THE GT INTRINSICS;
+ *   scored:    valid set, t != floor(query t), zg finite and > 0;
+ *   eligible:  scored, gt visible, ze finite and > 0;
+ *   ratio:     r = |G| / |E| with |P| = sqrtf((X * X + Y * Y) + Z * Z);
+ *   scale s of track i:
+ *     L4P_TRACK3D_SCALE_NONE          s = 1;
+ *     L4P_TRACK3D_SCALE_MEDIAN        the lower median (rank (c - 1) / 2, torch.median) of r over the c eligible frames of the
+ *                                     clip, NaN when c = 0;
+ *     L4P_TRACK3D_SCALE_TRACK_MEDIAN  the lower median of r over the eligible frames of track i alone, NaN when it has none;
+ *     L4P_TRACK3D_SCALE_QUERY         zg / ze at frame floor(query t): that frame must lie in [0, T), have valid set (NULL = set)
+ *                                     and both depths finite and > 0, otherwise NaN;
+ *   distance:  dx = s * Ex - Gx, dy, dz likewise, d = sqrtf((dx * dx + dy * dy) + dz * dz);
+ *   thresholds, depth-adaptive in TAP-Vid's 256 x 256 frame: sx = 256.f / W, sy = 256.f / H, f = sqrtf((fx * sx) * (fy * sy)),
+ *     u = zg / f, and for thr in {1, 2, 4, 8, 16} within = d < (float)thr * u.
+ * A NaN scale (or a NaN distance: a missing estimate) makes every `within` of the frame false; the frame stays in the
+ * denominators - a miss, not an exclusion.  Predicted visible is vis_logit > 0.  counts [B][L4P_METRIC_TRACKS_COUNTS] (workspace,
+ * cleared here) and out[0..30] have exactly the layout and the formulas of l4p_metric_tracks.  out[31] = the clip's s for
+ * L4P_TRACK3D_SCALE_NONE / _MEDIAN, the number of tracks with a finite scale for _TRACK_MEDIAN / _QUERY.  The ratios are expected
+ * not to be NaN (finite coordinates); a NaN ratio sorts above every other.
+ * Refused: B, N, T, H or W < 1, B * N * T >= 2^31, an unknown scale, a NULL pointer other than valid, ws_bytes below
+ * l4p_metric_tracks3d_ws_bytes(B, N, T, scale) (0 for arguments the entry refuses). */
+#define L4P_TRACK3D_SCALE_NONE 0
+#define L4P_TRACK3D_SCALE_MEDIAN 1
+#define L4P_TRACK3D_SCALE_TRACK_MEDIAN 2
+#define L4P_TRACK3D_SCALE_QUERY 3
+size_t l4p_metric_tracks3d_ws_bytes(int B, int N, int T, int scale);
+int l4p_metric_tracks3d(l4p_stream stream, const float* traj_est, const float* traj_gt, const float* depth_est, const float* depth_gt,
+                        const float* vis_logit, const unsigned char* vis_gt, const unsigned char* valid, const float* queries,
+                        const float* intrinsics, int B, int N, int T, int H, int W, int scale, void* ws, size_t ws_bytes,
+                        unsigned long long* counts, double* out);
 /* Cameras, ATE / RPE with the RMSE statistic: pose_est [B][16][T] row-major world_T_cam (traj3d_est_b16t), extr_gt [B][4][4][T]
  * cam_T_world (extrinsics_b44t, inverted in f64: G).  f64 throughout.  The closed-form similarity (s, R, t) of the estimated onto
  * the gt camera centres over all T frames (Umeyama, reflection case included, no RANSAC), then out[0] = ate = RMSE of

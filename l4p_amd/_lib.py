@@ -14,7 +14,7 @@ L4P_BF16 = 0
 L4P_F32 = 1
 L4P_F16 = 2  # IEEE half storage / f16 MFMA: the arithmetic class of the reference's "16-mixed" (fp16 autocast)
 
-ABI_VERSION = 18  # what l4p_abi_version() of the library this binding was written against returns (include/l4p_hip.h)
+ABI_VERSION = 19  # what l4p_abi_version() of the library this binding was written against returns (include/l4p_hip.h)
 
 EPI_DENSE, EPI_QKV, EPI_CONVT, EPI_MASKDOT = 0, 1, 2, 3
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
@@ -156,6 +156,10 @@ SIGNATURES = {
     "l4p_metric_mask": (_I, [_VP, _VP, _VP, _VP, _I, _LL, _VP, _SZ, _VP]),
     "l4p_metric_tracks": (_I, [_VP] * 7 + [_I] * 5 + [_VP, _VP]),
     "l4p_metric_cameras": (_I, [_VP, _VP, _VP, _I, _I, _VP]),
+    "l4p_metric_depth_full_ws_bytes": (_SZ, [_I, _LL, _I]),
+    "l4p_metric_depth_full": (_I, [_VP, _VP, _VP, _VP, _I, _LL, _I, _F, _F, _VP, _SZ, _VP]),
+    "l4p_metric_tracks3d_ws_bytes": (_SZ, [_I, _I, _I, _I]),
+    "l4p_metric_tracks3d": (_I, [_VP] * 10 + [_I] * 6 + [_VP, _SZ, _VP, _VP]),
     "l4p_layernorm_ex": (_I, [_VP, _I, _VP, _VP, _VP, _F, _VP, _VP, _I, _I, _VP, _I, _VP, _I]),
     "l4p_gemm_group": (_I, [_VP, _I, _VP, _I]),
     "l4p_layernorm_res": (_I, [_VP, _I, _VP, _I, _VP, _VP, _VP, _F, _VP, _VP, _I, _I, _VP, _I, _VP, _VP, _I, _I, _VP]),

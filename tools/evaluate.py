@@ -7,7 +7,11 @@ Each .npz holds one clip as a dataset's __getitem__ yields it: arrays under the 
 
 Prints one JSON line per clip (the scalars of that clip) and one with the mean of each metric over the clips that have a value.
 
-  python tools/evaluate.py CLIPS_DIR --ckpt model.ckpt [--precision 16-mixed] [--depth-align median|none|lstsq]
+  python tools/evaluate.py CLIPS_DIR --ckpt model.ckpt [--precision 16-mixed] [--depth-align median|none|lstsq|lstsq_inv]
+                           [--depth-log-errors] [--track-3d none|median|track_median|query]
+
+--depth-align lstsq_inv fits scale and shift in inverse depth; --depth-log-errors adds depth_sq_rel / rmse_log / log10 / silog;
+--track-3d MODE scores the (x, y, z) tracks in camera space (clips with track_2d_depth_bn1t and intrinsics_b44t) with the scale MODE.
   python tools/evaluate.py CLIPS_DIR --synthetic [--mini]      # seeded weights, as demo/demo.py --synthetic: plumbing, not numbers
 
 With --raw the .npz files hold RAW clips instead (the dataset's own resolution and length, rgb as float in [0, 1] or uint8): they
@@ -88,7 +92,7 @@ def write_synthetic_raw(clips: str, n: int = 2, T: int = 9, H: int = 56, W: int 
         np.savez(os.path.join(clips, f"synthetic_{i}.npz"), **synthetic_ground_truth(40 + i, T, H, W, N))
 
 
-def main():
+def parse_args(argv=None):
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("clips", help="directory of .npz clips")
     ap.add_argument("--ckpt", default=None)
@@ -97,16 +101,24 @@ def main():
     ap.add_argument("--mini", action="store_true", help="with --synthetic: the mini geometry of the test-suite")
     ap.add_argument("--max-queries", type=int, default=128)
     ap.add_argument("--precision", default="16-mixed")
-    ap.add_argument("--depth-align", default="median", choices=["median", "none", "lstsq"])
+    ap.add_argument("--depth-align", default="median", choices=["median", "none", "lstsq", "lstsq_inv"])
+    ap.add_argument("--depth-log-errors", action="store_true", help="also depth_sq_rel, depth_rmse_log, depth_log10, depth_silog")
+    ap.add_argument("--track-3d", default=None, choices=["none", "median", "track_median", "query"], metavar="MODE",
+                    help="score the 3D tracks with this scale: none, median (per clip), track_median, query (per track)")
     ap.add_argument("--raw", action="store_true", help="the .npz files are raw clips: prepare them with NpzClipDataset on the GPU")
     ap.add_argument("--resize", type=int, nargs=2, default=None, metavar=("H", "W"), help="with --raw: resize_size")
     ap.add_argument("--crop", type=int, nargs=3, default=None, metavar=("T", "H", "W"), help="with --raw: crop_size (default: the "
                     "clip's length rounded up to a multiple of 8, at least 16, x 224 x 224)")
     ap.add_argument("--spacing", type=float, default=0.02, help="with --raw: grid spacing of the queries of clips without tracks")
     ap.add_argument("--seed", type=int, default=0, help="with --raw: torch.manual_seed before the clips are drawn")
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     if not args.synthetic and not args.ckpt:
         ap.error("--ckpt (or --synthetic)")
+    return ap, args
+
+
+def main():
+    ap, args = parse_args()
     if args.raw and args.synthetic and not glob.glob(os.path.join(args.clips, "*.npz")):
         write_synthetic_raw(args.clips)
     files = sorted(glob.glob(os.path.join(args.clips, "*.npz")))
@@ -130,7 +142,7 @@ def main():
     else:
         model = prepare_model(model_config_path=args.config, ckpt_path=args.ckpt, max_queries=args.max_queries,
                               precision=args.precision, accelerator="gpu")
-    model.metrics_module = L4PMetrics(depth_align=args.depth_align)
+    model.metrics_module = L4PMetrics(depth_align=args.depth_align, track_3d=args.track_3d, depth_log_errors=args.depth_log_errors)
     rows = []
 
     def batches():
