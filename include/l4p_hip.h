@@ -43,7 +43,8 @@ typedef void* l4p_stream; /* hipStream_t */
 typedef struct l4p_engine l4p_engine;
 
 const char* l4p_last_error(void);
-int l4p_abi_version(void); /* 19: 3D-track metrics, inverse-depth alignment and log-space depth errors (l4p_metric_tracks3d,
+int l4p_abi_version(void); /* 20: the split-K rule of the 3x3x3 conv, stated once for caller and launcher (l4p_conv3d_splitk);
+                              * 19: 3D-track metrics, inverse-depth alignment and log-space depth errors (l4p_metric_tracks3d,
                               * l4p_metric_tracks3d_ws_bytes, l4p_metric_depth_full, l4p_metric_depth_full_ws_bytes);
                               * 18: the L4PDataset base class (l4p_gt_dense_clip, l4p_gt_query_select, l4p_gt_tracks_clip);
                               * 17: evaluation metrics (l4p_metric_ws_bytes, l4p_metric_depth, l4p_metric_flow, l4p_metric_mask,
@@ -269,6 +270,10 @@ int l4p_gemm(l4p_stream stream, int dtype, const l4p_gemm_desc* d);
 #define L4P_GEMM_GROUP_MAX 4
 int l4p_gemm_group(l4p_stream stream, int dtype, const l4p_gemm_desc* d, int n);
 int l4p_conv3d_k3(l4p_stream stream, int dtype, const l4p_gemm_desc* d);
+/* The split-K factor the engine gives a 3x3x3 conv of M output voxels, N output channels and K = 27 * Cin (l4p_gemm_desc.splitk:
+ * 1 = none, at most 16): the caller of l4p_conv3d_k3 allocates partial[splitk][M][N], so caller and l4p_dpt_forward read the one
+ * rule.  Pure host arithmetic, no GPU needed; 0 for an unknown dtype or a size < 1. */
+int l4p_conv3d_splitk(long long M, int N, int K, int dtype);
 /* Sub-pixel conv: nn.ConvTranspose3d with kernel == stride == (kt, kh, kw) followed by nn.Conv3d 3x3x3, pad 1, no bias
  * (dpt_block.py:255-276: act_postprocess[i][1] -> scratch.layer_rn[i]) as one implicit GEMM over the LOW-resolution grid.
  *   A       channels-last [B][Ti][Hi][Wi][Cin] T;  M = B*Ti*Hi*Wi

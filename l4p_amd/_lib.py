@@ -14,7 +14,7 @@ L4P_BF16 = 0
 L4P_F32 = 1
 L4P_F16 = 2  # IEEE half storage / f16 MFMA: the arithmetic class of the reference's "16-mixed" (fp16 autocast)
 
-ABI_VERSION = 19  # what l4p_abi_version() of the library this binding was written against returns (include/l4p_hip.h)
+ABI_VERSION = 20  # what l4p_abi_version() of the library this binding was written against returns (include/l4p_hip.h)
 
 EPI_DENSE, EPI_QKV, EPI_CONVT, EPI_MASKDOT = 0, 1, 2, 3
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
@@ -116,6 +116,7 @@ SIGNATURES = {
     "l4p_prof_detail": (_LL, [C.c_char_p, _LL]),
     "l4p_gemm": (_I, [_VP, _I, C.POINTER(GemmDesc)]),
     "l4p_conv3d_k3": (_I, [_VP, _I, C.POINTER(GemmDesc)]),
+    "l4p_conv3d_splitk": (_I, [_LL, _I, _I, _I]),
     "l4p_conv3d_subpixel": (_I, [_VP, _I, C.POINTER(GemmDesc)]),
     "l4p_layernorm": (_I, [_VP, _I, _VP, _VP, _VP, _F, _VP, _VP, _I, _I]),
     "l4p_attention": (_I, [_VP, _I, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _F]),

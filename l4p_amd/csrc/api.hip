@@ -10,7 +10,8 @@
 
 #include <stdlib.h>
 
-#include "engine.hpp"
+#include "gemm_select.hpp"
+#include "graph.hpp"
 
 static thread_local char g_err[512] = "";
 
@@ -24,7 +25,7 @@ void l4p_set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* l4p_last_error(void) { return g_err; }
-int l4p_abi_version(void) { return 19; }
+int l4p_abi_version(void) { return 20; }
 
 // A HIP stream whose kernels run on CUs [first_cu, first_cu + n_cus) only (hipExtStreamCreateWithCUMask): the sharded long-video path
 // gives the tracker's latency-bound kernel chain a slice of the chip of its own, beside the chip-filling decoders on the rest.
@@ -65,6 +66,10 @@ int l4p_conv3d_k3(l4p_stream stream, int dtype, const l4p_gemm_desc* d) {
         return L4P_E_INVALID;
     }
     return launch_gemm(dtype, 1, *d, (hipStream_t)stream);
+}
+int l4p_conv3d_splitk(long long M, int N, int K, int dtype) {
+    if (!dtype_ok(dtype) || M < 1 || N < 1 || K < 1) return 0;
+    return conv3d_splitk(M, N, K, esize_of(dtype));
 }
 int l4p_conv3d_subpixel(l4p_stream stream, int dtype, const l4p_gemm_desc* d) {
     if (!d) {
@@ -219,24 +224,18 @@ size_t l4p_encoder_workspace_bytes(const l4p_engine* e, int B) {
     return enc_layout(e, B, nullptr).total;
 }
 
-#define GETW(var, key)                                                  \
-    const void* var = e->find(key);                                     \
-    if (!var) {                                                         \
-        l4p_set_error("weight '%s' was never bound", std::string(key).c_str()); \
-        return L4P_E_MISSING;                                           \
-    }
-
 int l4p_encoder_forward(l4p_engine* e, l4p_stream stream_, const float* rgb, int B, void* workspace, size_t ws_bytes,
                         int n_taps, const int* tap_layer, float* const* tap_f32, void* const* tap_T) {
     if (!e || !e->enc_set || !rgb || !workspace || B <= 0 || n_taps <= 0) {
         l4p_set_error("l4p_encoder_forward: bad arguments");
         return L4P_E_INVALID;
     }
-    hipStream_t stream = (hipStream_t)stream_;
     const l4p_encoder_cfg& c = e->enc;
     const int dt = e->dtype;
     const size_t es = esize_of(dt);
     const int S = e->enc_tokens, M = B * S, C = c.dim, H = c.heads, Dh = c.head_dim, Dp = 96;
+    // (the workspace is the explicit layout above - its slots alias on purpose - not the graph's allocator: g carries the weight
+    //  lookup and the launch guard)
     EncWs w = enc_layout(e, B, (char*)workspace);
     if (ws_bytes < w.total) {
         l4p_set_error("l4p_encoder_forward: workspace too small (%zu < %zu)", ws_bytes, w.total);
@@ -250,68 +249,42 @@ int l4p_encoder_forward(l4p_engine* e, l4p_stream stream_, const float* rgb, int
         }
         if (tap_layer[i] > last) last = tap_layer[i];
     }
-    int rc;
-    auto emit_taps = [&](int layer) -> int {
+    Graph g(e, "l4p_encoder_forward", "enc.");
+    g.on(stream_, workspace, ws_bytes);
+    hipStream_t stream = g.st;
+    auto emit_taps = [&](int layer) {
         for (int i = 0; i < n_taps; ++i) {
             if (tap_layer[i] != layer) continue;
             if (layer == c.depth) {
                 // features_list[-1] = norm(x)  (l4p_videomae.py:115)
-                const void* g = e->find("enc.norm.g");
-                const void* b = e->find("enc.norm.b");
-                if (!g || !b) {
-                    l4p_set_error("weight 'enc.norm.*' was never bound");
-                    return L4P_E_MISSING;
-                }
-                int r = launch_layernorm(dt, w.x, (const float*)g, (const float*)b, c.ln_eps, tap_T ? tap_T[i] : nullptr,
-                                         tap_f32 ? tap_f32[i] : nullptr, M, C, stream);
-                if (r) return r;
+                const float *ng = g.Wf("norm.g"), *nb = g.Wf("norm.b");
+                g.launch([&] {
+                    return launch_layernorm(dt, w.x, ng, nb, c.ln_eps, tap_T ? tap_T[i] : nullptr, tap_f32 ? tap_f32[i] : nullptr, M, C, stream);
+                });
             } else {
-                if (tap_f32 && tap_f32[i]) {
-                    hipError_t he = hipMemcpyAsync(tap_f32[i], w.x, (size_t)M * C * 4, hipMemcpyDeviceToDevice, stream);
-                    if (he != hipSuccess) {
+                if (tap_f32 && tap_f32[i])
+                    g.launch([&] {
+                        hipError_t he = hipMemcpyAsync(tap_f32[i], w.x, (size_t)M * C * 4, hipMemcpyDeviceToDevice, stream);
+                        if (he == hipSuccess) return 0;
                         l4p_set_error("tap copy failed: %s", hipGetErrorString(he));
                         return L4P_E_HIP;
-                    }
-                }
-                if (tap_T && tap_T[i]) {
-                    int r = launch_cast(dt, w.x, tap_T[i], (long long)M * C, stream);
-                    if (r) return r;
-                }
+                    });
+                if (tap_T && tap_T[i]) g.launch([&] { return launch_cast(dt, w.x, tap_T[i], (long long)M * C, stream); });
             }
         }
-        return 0;
     };
 
     // ---- patch embed: gather -> GEMM (+bias, + fixed sinusoid table)   modeling_finetune.py:276-283,
     //      l4p_videomae.py:99-101
     {
-        GETW(pw_, "enc.patch.w");
-        GETW(pb_, "enc.patch.b");
-        GETW(pos_, "enc.pos");
-        rc = launch_patch_gather(dt, rgb, w.xn, B, c.in_chans, c.frames, c.img_h, c.img_w, c.pt, c.ph, c.pw, c.patch_kp,
-                                 stream);
-        if (rc) return rc;
-        GemmParams p;
-        memset(&p, 0, sizeof(p));
-        p.A = w.xn;
-        p.lda = c.patch_kp;
-        p.W = pw_;
-        p.ldw = c.patch_kp;
-        p.M = M;
-        p.N = C;
-        p.K = c.patch_kp;
-        p.bias = (const float*)pb_;
-        p.res1 = pos_;
-        p.res_f32 = 1;
-        p.ldr = C;
-        p.res_mod = S;
-        p.out_f32 = w.x;
-        p.ldc = C;
-        rc = launch_gemm(dt, 0, p, stream);
-        if (rc) return rc;
+        GemmParams p = dense(w.xn, M, c.patch_kp, c.patch_kp, g.W("patch.w"), c.patch_kp, C);
+        p.bias = g.Wf("patch.b");
+        p.res1 = g.W("pos"), p.res_f32 = 1, p.ldr = C, p.res_mod = S;
+        p.out_f32 = w.x, p.ldc = C;
+        g.launch([&] { return launch_patch_gather(dt, rgb, w.xn, B, c.in_chans, c.frames, c.img_h, c.img_w, c.pt, c.ph, c.pw, c.patch_kp, stream); });
+        g.gemm(0, p);
     }
-    rc = emit_taps(0);
-    if (rc) return rc;
+    emit_taps(0);
 
     const float scale = 1.0f / sqrtf((float)Dh);
     // Deferred residual sums (bf16 engine): "x = x + proj(...)" and "x = x + fc2(...)" (modeling_finetune.py:247-248) are not formed
@@ -327,110 +300,66 @@ int l4p_encoder_forward(l4p_engine* e, l4p_stream stream_, const float* rgb, int
     bool pending = false;
     int pending_sk = 0;
     const float* pending_bias = nullptr;
-    char key[96];
-    for (int l = 0; l < last && l < c.depth; ++l) {
-#define BW(var, suffix)                                  \
-    snprintf(key, sizeof(key), "enc.blk%d." suffix, l);  \
-    GETW(var, key)
-        BW(ln1g, "ln1.g");
-        BW(ln1b, "ln1.b");
-        BW(qkvw, "qkv.w");
-        BW(qkvb, "qkv.b");
-        BW(projw, "proj.w");
-        BW(projb, "proj.b");
-        BW(ln2g, "ln2.g");
-        BW(ln2b, "ln2.b");
-        BW(fc1w, "fc1.w");
-        BW(fc1b, "fc1.b");
-        BW(fc2w, "fc2.w");
-        BW(fc2b, "fc2.b");
-#undef BW
+    for (int l = 0; l < last && l < c.depth && !g.rc; ++l) {
+        char key[48];
+        auto Wb = [&](const char* name) {
+            snprintf(key, sizeof(key), "blk%d.%s", l, name);
+            return g.W(key);
+        };
+        auto Wbf = [&](const char* name) { return (const float*)Wb(name); };
+        // (all of a block's weights before its first launch: a missing one stops the forward at a block boundary)
+        const void *qkvw = Wb("qkv.w"), *projw = Wb("proj.w"), *fc1w = Wb("fc1.w"), *fc2w = Wb("fc2.w");
+        const float *ln1g = Wbf("ln1.g"), *ln1b = Wbf("ln1.b"), *ln2g = Wbf("ln2.g"), *ln2b = Wbf("ln2.b");
+        const float *qkvb = Wbf("qkv.b"), *projb = Wbf("proj.b"), *fc1b = Wbf("fc1.b"), *fc2b = Wbf("fc2.b");
         // x = x + proj(attn(norm1(x)))            modeling_finetune.py:247, :169-190
         if (pending) {  // x += the previous block's MLP output (left in the engine dtype), then norm1: one pass over x
-            rc = launch_layernorm_res(dt, w.x, 0, delta, (const float*)ln1g, (const float*)ln1b, c.ln_eps, w.xn, nullptr, M, C, nullptr, 0,
-                                      nullptr, nullptr, 1, 0, stream, w.x);
+            g.launch([&] {
+                return launch_layernorm_res(dt, w.x, 0, delta, ln1g, ln1b, c.ln_eps, w.xn, nullptr, M, C, nullptr, 0, nullptr, nullptr, 1, 0,
+                                            stream, w.x);
+            });
             pending = false;
         } else if (pending_sk > 0) {  // ... left as split-K partials: bias + slices summed here instead of in a finish pass
-            rc = launch_layernorm_res(dt, w.x, 0, nullptr, (const float*)ln1g, (const float*)ln1b, c.ln_eps, w.xn, nullptr, M, C,
-                                      nullptr, 0, nullptr, nullptr, 1, 0, stream, w.x, w.sk, pending_sk, pending_bias);
+            g.launch([&] {
+                return launch_layernorm_res(dt, w.x, 0, nullptr, ln1g, ln1b, c.ln_eps, w.xn, nullptr, M, C, nullptr, 0, nullptr, nullptr, 1, 0,
+                                            stream, w.x, w.sk, pending_sk, pending_bias);
+            });
             pending_sk = 0;
         } else {
-            rc = launch_layernorm(dt, w.x, (const float*)ln1g, (const float*)ln1b, c.ln_eps, w.xn, nullptr, M, C, stream);
+            g.launch([&] { return launch_layernorm(dt, w.x, ln1g, ln1b, c.ln_eps, w.xn, nullptr, M, C, stream); });
         }
-        if (rc) return rc;
-        GemmParams p;
-        memset(&p, 0, sizeof(p));
-        p.A = w.xn;
-        p.lda = C;
-        p.W = qkvw;
-        p.ldw = C;
-        p.M = M;
-        p.N = 3 * H * Dp;
-        p.K = C;
-        p.bias = (const float*)qkvb;
+        GemmParams p = dense(w.xn, M, C, C, qkvw, C, 3 * H * Dp);
+        p.bias = qkvb;
         p.out_T = w.qk;  // q: [M][H*Dp]; k (tile order) follows in the same workspace slot
         p.k_tiled = w.qk + (size_t)M * H * Dp * es;
         p.ldc = H * Dp;
         p.epi = EPI_QKV;
-        p.vt = w.vt;
-        p.S = S;
-        p.H = H;
-        p.Dp = Dp;
+        p.vt = w.vt, p.S = S, p.H = H, p.Dp = Dp;
         p.q_scale = scale * 1.4426950408889634f;  // q leaves the projection in the exp2 domain: one rounding of q * scale
-        rc = launch_gemm(dt, 0, p, stream);
-        if (rc) return rc;
-        rc = launch_attention(dt, w.qk, w.qk + (size_t)M * H * Dp * es, w.vt, w.ao, B, S, H, Dh, L4P_ATTN_PRESCALED, stream);
-        if (rc) return rc;
-        memset(&p, 0, sizeof(p));
-        p.A = w.ao;
-        p.lda = C;
-        p.W = projw;
-        p.ldw = C;
-        p.M = M;
-        p.N = C;
-        p.K = C;
-        p.bias = (const float*)projb;
+        g.gemm(0, p);
+        g.launch([&] { return launch_attention(dt, w.qk, w.qk + (size_t)M * H * Dp * es, w.vt, w.ao, B, S, H, Dh, L4P_ATTN_PRESCALED, stream); });
+        p = dense(w.ao, M, C, C, projw, C, C);
+        p.bias = projb;
         p.ldc = C;
-        if (defer) {  // (q / k are dead once the attention has run: their slot takes the projection's output)
+        if (defer)  // (q / k are dead once the attention has run: their slot takes the projection's output)
             p.out_T = delta;
-        } else {
-            p.res1 = w.x;
-            p.res_f32 = 1;
-            p.ldr = C;
-            p.out_f32 = w.x;
-        }
-        rc = launch_gemm(dt, 0, p, stream);
-        if (rc) return rc;
+        else
+            p.res1 = w.x, p.res_f32 = 1, p.ldr = C, p.out_f32 = w.x;
+        g.gemm(0, p);
         // x = x + fc2(gelu(fc1(norm2(x))))         modeling_finetune.py:248, :62-69
         if (defer)
-            rc = launch_layernorm_res(dt, w.x, 0, delta, (const float*)ln2g, (const float*)ln2b, c.ln_eps, w.xn, nullptr, M, C, nullptr, 0,
-                                      nullptr, nullptr, 1, 0, stream, w.x);
+            g.launch([&] {
+                return launch_layernorm_res(dt, w.x, 0, delta, ln2g, ln2b, c.ln_eps, w.xn, nullptr, M, C, nullptr, 0, nullptr, nullptr, 1, 0,
+                                            stream, w.x);
+            });
         else
-            rc = launch_layernorm(dt, w.x, (const float*)ln2g, (const float*)ln2b, c.ln_eps, w.xn, nullptr, M, C, stream);
-        if (rc) return rc;
-        memset(&p, 0, sizeof(p));
-        p.A = w.xn;
-        p.lda = C;
-        p.W = fc1w;
-        p.ldw = C;
-        p.M = M;
-        p.N = c.mlp_hidden;
-        p.K = C;
-        p.bias = (const float*)fc1b;
+            g.launch([&] { return launch_layernorm(dt, w.x, ln2g, ln2b, c.ln_eps, w.xn, nullptr, M, C, stream); });
+        p = dense(w.xn, M, C, C, fc1w, C, c.mlp_hidden);
+        p.bias = fc1b;
         p.act = ACT_GELU;
-        p.out_T = w.hb;
-        p.ldc = c.mlp_hidden;
-        rc = launch_gemm(dt, 0, p, stream);
-        if (rc) return rc;
-        memset(&p, 0, sizeof(p));
-        p.A = w.hb;
-        p.lda = c.mlp_hidden;
-        p.W = fc2w;
-        p.ldw = c.mlp_hidden;
-        p.M = M;
-        p.N = C;
-        p.K = c.mlp_hidden;
-        p.bias = (const float*)fc2b;
+        p.out_T = w.hb, p.ldc = c.mlp_hidden;
+        g.gemm(0, p);
+        p = dense(w.hb, M, c.mlp_hidden, c.mlp_hidden, fc2w, c.mlp_hidden, C);
+        p.bias = fc2b;
         p.ldc = C;
         p.splitk = enc_fc2_splitk(e, (size_t)M);
         p.partial = p.splitk > 1 ? w.sk : nullptr;
@@ -446,26 +375,15 @@ int l4p_encoder_forward(l4p_engine* e, l4p_stream stream_, const float* rgb, int
             // partials and read + wrote x only for the LayerNorm to read x again)
             p.tuning |= 2;
             pending_sk = p.splitk;
-            pending_bias = (const float*)fc2b;
+            pending_bias = fc2b;
         } else {
-            p.res1 = w.x;
-            p.res_f32 = 1;
-            p.ldr = C;
-            p.out_f32 = w.x;
+            p.res1 = w.x, p.res_f32 = 1, p.ldr = C, p.out_f32 = w.x;
         }
-        rc = launch_gemm(dt, 0, p, stream);
-        if (rc) return rc;
-        if (l + 1 < c.depth) {
-            rc = emit_taps(l + 1);
-            if (rc) return rc;
-        }
+        g.gemm(0, p);
+        if (l + 1 < c.depth) emit_taps(l + 1);
     }
-    if (last == c.depth) {
-        rc = emit_taps(c.depth);
-        if (rc) return rc;
-    }
-    (void)es;
-    return 0;
+    if (last == c.depth) emit_taps(c.depth);
+    return g.rc;
 }
 
 }  // extern "C"

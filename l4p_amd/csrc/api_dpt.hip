@@ -1,27 +1,16 @@
 // l4p_dpt_forward: the whole DPT decoder of one dense head (reference DPTOutputAdapter_fix.forward,
 // dpt_head.py:41-86 + dpt_block.py:93-157,210-238,255-278,406-414) as ONE native call: ~45 kernel launches
 // issued back to back from C++ on the caller's stream, intermediates bump-allocated from a caller-provided
-// workspace.  Same kernels, same order and same arguments as the Python composition in
-// l4p_amd/models/task_heads/dense_heads.py (dpt_decode), which remains as the readable statement of the graph
-// and is asserted bit-identical in tests/test_encoder_dpt_gpu.py.
-#include <string.h>
-
-#include <string>
-
-#include "engine.hpp"
+// workspace (graph.hpp).  This file is the one statement of the decoder's graph: every model forward, the benchmark and the
+// tests run it, its dispatch switches are knobs (dpt_fold_rn, conv_ups), and l4p_amd/ops.py reaches the same kernels one by
+// one for the per-kernel parity tests.
+// One algebraic re-ordering against the reference: FeatureFusionBlock's out_conv (1x1x1) runs BEFORE the trilinear
+// up-sampling instead of after it (dpt_block.py:229-237); both are linear and the interpolation weights sum to one.
+// The allocator never releases here (the peak is the final offset); l4p_dpt_workspace_bytes is a dry run of run().
+#include "gemm_select.hpp"
+#include "graph.hpp"
 
 namespace {
-
-struct Bump {
-    char* base;
-    size_t off, cap;
-    bool dry;  // size query: no memory behind it
-    void* take(size_t bytes) {
-        const size_t a = (off + 255) & ~(size_t)255;
-        off = a + bytes;
-        return dry ? (void*)1 : (off <= cap ? base + a : nullptr);
-    }
-};
 
 struct Vol {  // channels-last activation [B][t][h][w][c] of engine dtype
     void* p;
@@ -29,95 +18,31 @@ struct Vol {  // channels-last activation [B][t][h][w][c] of engine dtype
     long long vox(int B) const { return (long long)B * t * h * w; }
 };
 
-int splitk_for(long long M, int N, int K, int es) {  // keep in sync with l4p_amd/ops.py:splitk_for
-    const int nk = (K + 128 / es - 1) / (128 / es);
-    if (nk < 32) return 1;
-    long long s;
-    if (N >= 256) {  // 128x128 tiles, two workgroups per CU: aim at 512 workgroups (gemm_select.hpp picks the tile)
-        const long long tiles = ((M + 127) / 128) * ((N + 127) / 128);
-        if (tiles >= 400) return 1;
-        s = 512 / tiles;
-    } else {  // 128x64 tiles: ~1024 workgroups (4 per CU): one 4-wave workgroup per CU is latency-bound
-        const long long tiles = ((M + 127) / 128) * ((N + 63) / 64);
-        if (tiles >= 512) return 1;
-        s = 1024 / tiles;
-    }
-    if (s > 16) s = 16;
-    if (s > nk / 8) s = nk / 8;
-    return s < 1 ? 1 : (int)s;
-}
+struct Ctx : Graph {
+    int B;
+    Ctx(const l4p_engine* e_, int B_, std::string pre_ = std::string()) : Graph(e_, "l4p_dpt_forward", std::move(pre_)), B(B_) {}
 
-struct Ctx {
-    const l4p_engine* e;
-    hipStream_t st;
-    int dt, es, B;
-    Bump ws;
-    std::string pre;
-    int rc = 0;
-    bool dry = false;
+    Vol vol(int t, int h, int w, int c) { return Vol{T((long long)B * t * h * w, c), t, h, w, c}; }
 
-    const void* W(const std::string& k) {
-        if (dry) return (const void*)1;
-        const void* p = e->find(pre + k);
-        if (!p && !rc) {
-            l4p_set_error("weight '%s%s' was never bound", pre.c_str(), k.c_str());
-            rc = L4P_E_MISSING;
-        }
-        return p;
-    }
-    void* alloc(size_t bytes) {
-        void* p = ws.take(bytes);
-        if (!p && !rc) {
-            l4p_set_error("l4p_dpt_forward: workspace too small");
-            rc = L4P_E_INVALID;
-        }
-        return p;
-    }
-    Vol vol(int t, int h, int w, int c) { return Vol{alloc((size_t)B * t * h * w * c * es), t, h, w, c}; }
-
-    // out = act(x @ w^T + bias) on [vox][c] -> [vox][n]
-    Vol dense(const Vol& x, const char* wk, const char* bk, int n) {
+    // 1x1x1 conv: out = x @ w^T + bias on [vox][c] -> [vox][n]
+    Vol conv1(const Vol& x, const char* wk, const char* bk, int n) {
         Vol o = vol(x.t, x.h, x.w, n);
-        if (rc || dry) return o;
-        GemmParams p;
-        memset(&p, 0, sizeof(p));
-        p.A = x.p;
-        p.lda = x.c;
-        p.W = W(wk);
-        p.ldw = x.c;
-        p.M = (int)x.vox(B);
-        p.N = n;
-        p.K = x.c;
-        p.bias = (const float*)W(bk);
-        p.out_T = o.p;
-        p.ldc = n;
-        if (!rc) rc = launch_gemm(dt, 0, p, st);
+        GemmParams p = dense(x.p, x.vox(B), x.c, x.c, W(wk), x.c, n);
+        p.bias = Wf(bk);
+        p.out_T = o.p, p.ldc = n;
+        gemm(0, p);
         return o;
     }
     // ConvTranspose3d kernel == stride == k
     Vol convT(const Vol& x, const char* wk, const char* bk, int cout, const int k[3]) {
         Vol o = vol(x.t * k[0], x.h * k[1], x.w * k[2], cout);
-        if (rc || dry) return o;
-        GemmParams p;
-        memset(&p, 0, sizeof(p));
-        p.A = x.p;
-        p.lda = x.c;
-        p.W = W(wk);
-        p.ldw = x.c;
-        p.M = (int)x.vox(B);
-        p.N = k[0] * k[1] * k[2] * cout;
-        p.K = x.c;
-        p.Ti = x.t;
-        p.Hi = x.h;
-        p.Wi = x.w;
-        p.bias = (const float*)W(bk);
+        GemmParams p = dense(x.p, x.vox(B), x.c, x.c, W(wk), x.c, k[0] * k[1] * k[2] * cout);
+        p.Ti = x.t, p.Hi = x.h, p.Wi = x.w;
+        p.bias = Wf(bk);
         p.out_T = o.p;
         p.epi = EPI_CONVT;
-        p.kt = k[0];
-        p.kh = k[1];
-        p.kw = k[2];
-        p.Cout = cout;
-        if (!rc) rc = launch_gemm(dt, 0, p, st);
+        p.kt = k[0], p.kh = k[1], p.kw = k[2], p.Cout = cout;
+        gemm(0, p);
         return o;
     }
     // ConvTranspose3d kernel == stride == k followed by the bias-free 3x3x3 conv, folded at pack time into one sub-pixel conv over
@@ -132,27 +57,14 @@ struct Ctx {
     Vol fold(const Vol& x, const char* wk, const char* bk, int cout, const int k[3], Vol* relu_copy) {
         Vol o = vol(x.t * k[0], x.h * k[1], x.w * k[2], cout);
         if (relu_copy) *relu_copy = vol(o.t, o.h, o.w, cout);
-        if (rc || dry) return o;
-        GemmParams p;
-        memset(&p, 0, sizeof(p));
-        p.A = x.p;
-        p.W = W(wk);
-        p.ldw = (long long)(k[0] == 1 ? 3 : 2) * (k[1] == 1 ? 3 : 2) * (k[2] == 1 ? 3 : 2) * x.c;
-        p.M = (int)x.vox(B);
-        p.N = k[0] * k[1] * k[2] * cout;
-        p.K = (int)p.ldw;
-        p.Ti = x.t;
-        p.Hi = x.h;
-        p.Wi = x.w;
-        p.Cin = x.c;
-        p.bias = (const float*)W(bk);
+        const int cells = (k[0] == 1 ? 3 : 2) * (k[1] == 1 ? 3 : 2) * (k[2] == 1 ? 3 : 2);
+        GemmParams p = dense(x.p, x.vox(B), cells * x.c, 0, W(wk), (long long)cells * x.c, k[0] * k[1] * k[2] * cout);
+        p.Ti = x.t, p.Hi = x.h, p.Wi = x.w, p.Cin = x.c;
+        p.bias = Wf(bk);
         p.out_T = o.p;
         p.out_relu_T = relu_copy ? relu_copy->p : nullptr;
-        p.kt = k[0];
-        p.kh = k[1];
-        p.kw = k[2];
-        p.Cout = cout;
-        if (!rc) rc = launch_gemm(dt, 2, p, st);
+        p.kt = k[0], p.kh = k[1], p.kw = k[2], p.Cout = cout;
+        gemm(2, p);
         return o;
     }
     // 3x3x3 conv, pad 1; optional bias / ReLU output / two T residuals / relu copy
@@ -164,49 +76,27 @@ struct Ctx {
         Vol o = vol((x.t - 1) / s[0] + 1, (x.h - 1) / s[1] + 1, (x.w - 1) / s[2] + 1, cout);
         if (relu_copy) *relu_copy = vol(o.t, o.h, o.w, cout);
         const long long M = o.vox(B);
-        const int sk = ups_h > 0 ? 1 : splitk_for(M, cout, 27 * x.c, es);
-        float* partial = sk > 1 ? (float*)alloc((size_t)sk * M * cout * 4) : nullptr;
-        if (rc || dry) return o;
-        GemmParams p;
-        memset(&p, 0, sizeof(p));
-        p.A = x.p;
-        p.W = W(wk);
-        p.ldw = 27 * x.c;
-        p.M = (int)M;
-        p.N = cout;
-        p.K = 27 * x.c;
-        p.Ti = x.t;
-        p.Hi = x.h;
-        p.Wi = x.w;
-        p.Cin = x.c;
-        p.To = o.t;
-        p.Ho = o.h;
-        p.Wo = o.w;
-        p.st = s[0];
-        p.sh = s[1];
-        p.sw = s[2];
-        p.bias = bk ? (const float*)W(bk) : nullptr;
+        // (the caller of l4p_conv3d_k3 owns the split-K partials: l4p_conv3d_splitk is the rule for both sides)
+        const int sk = ups_h > 0 ? 1 : conv3d_splitk(M, cout, 27 * x.c, es);
+        float* partial = sk > 1 ? f32((long long)sk * M, cout) : nullptr;
+        GemmParams p = dense(x.p, M, 27 * x.c, 0, W(wk), 27 * x.c, cout);
+        p.Ti = x.t, p.Hi = x.h, p.Wi = x.w, p.Cin = x.c;
+        p.To = o.t, p.Ho = o.h, p.Wo = o.w;
+        p.st = s[0], p.sh = s[1], p.sw = s[2];
+        p.bias = bk ? Wf(bk) : nullptr;
         p.act = act;
-        if (r1) {
-            p.res1 = r1;
-            p.res2 = r2;
-            p.res_f32 = 0;
-            p.ldr = cout;
-        }
-        p.out_T = o.p;
-        p.ldc = cout;
+        if (r1) p.res1 = r1, p.res2 = r2, p.res_f32 = 0, p.ldr = cout;
+        p.out_T = o.p, p.ldc = cout;
         p.out_relu_T = relu_copy ? relu_copy->p : nullptr;
-        p.splitk = sk;
-        p.partial = partial;
+        p.splitk = sk, p.partial = partial;
         if (ups_h > 0) p.ups_hi = x_in.h, p.ups_wi = x_in.w;
-        if (!rc) rc = launch_gemm(dt, 1, p, st);
+        gemm(1, p);
         return o;
     }
     Vol resize(const Vol& x, int t, int h, int w) {
         if (t == x.t && h == x.h && w == x.w) return x;
         Vol o = vol(t, h, w, x.c);
-        if (rc || dry) return o;
-        rc = launch_upsample(dt, x.p, o.p, B, x.t, x.h, x.w, t, h, w, x.c, 1, st);
+        launch([&] { return launch_upsample(dt, x.p, o.p, B, x.t, x.h, x.w, t, h, w, x.c, 1, st); });
         return o;
     }
 };
@@ -220,7 +110,7 @@ int run(Ctx& c, const l4p_dpt_cfg* cfg, const void* const* hooks, float* out) {
         char wk[32], bk[32];
         snprintf(wk, sizeof(wk), "act%d.0.w", i);
         snprintf(bk, sizeof(bk), "act%d.0.b", i);
-        Vol a = c.dense(tok, wk, bk, cfg->layer_dims[i]);
+        Vol a = c.conv1(tok, wk, bk, cfg->layer_dims[i]);
         const int* sf = cfg->actpost[i];
         snprintf(wk, sizeof(wk), "act%d.1.w", i);
         snprintf(bk, sizeof(bk), "act%d.1.b", i);
@@ -243,6 +133,9 @@ int run(Ctx& c, const l4p_dpt_cfg* cfg, const void* const* hooks, float* out) {
         snprintf(wk, sizeof(wk), "rn%d.w", i);
         lay[i] = c.conv3(a, wk, nullptr, F, one, ACT_NONE, nullptr, nullptr, &layr[i]);
     }
+    // ResidualConvUnit_custom (dpt_block.py:131-157): conv2(relu(conv1(relu(x)))) + x [+ extra].  relu(x) comes from the epilogue of
+    // the kernel that produced x (so conv1 streams its input by LDS-DMA); conv1's own ReLU is an output activation; the skip adds
+    // ride conv2's epilogue
     auto rcu = [&](int r, int u, const Vol& x, const Vol& xr, const void* extra, Vol* relu_copy) {
         char w1[40], b1[40], w2[40], b2[40];
         snprintf(w1, sizeof(w1), "ref%d.rcu%d.c1.w", r, u);
@@ -261,6 +154,8 @@ int run(Ctx& c, const l4p_dpt_cfg* cfg, const void* const* hooks, float* out) {
             orl = layr[3];
         } else {
             Vol p4 = path;
+            // dpt_head.py:70-72 crops refinenet4's output to layer 2's grid.  No geometry this engine is configured with reaches
+            // that (token grids with an even number of frames and rows: the stride-2 level doubles back exactly): refused
             if (r == 3 && (p4.t != lay[2].t || p4.h != lay[2].h)) {
                 l4p_set_error("l4p_dpt_forward: refinenet4 output needs cropping (unsupported token grid)");
                 return L4P_E_INVALID;
@@ -271,10 +166,9 @@ int run(Ctx& c, const l4p_dpt_cfg* cfg, const void* const* hooks, float* out) {
         char wk[32], bk[32];
         snprintf(wk, sizeof(wk), "ref%d.out.w", r);
         snprintf(bk, sizeof(bk), "ref%d.out.b", r);
-        Vol oc = c.dense(o2, wk, bk, F);  // out_conv commuted in front of the (linear) up-sampling
+        Vol oc = c.conv1(o2, wk, bk, F);  // out_conv commuted in front of the (linear) up-sampling
         const int* fs = cfg->fusion[i];
         path = c.resize(oc, oc.t * fs[0], oc.h * fs[1], oc.w * fs[2]);
-        if (c.rc) return c.rc;
     }
     Vol h1 = c.conv3(path, "head1.w", "head1.b", F / 2, one, ACT_NONE, nullptr, nullptr, nullptr);
     // dpt_head.py:79-84: interpolate -> head conv.  Knob conv_ups = 1 (off by default: measured slower, include/l4p_hip.h): where the
@@ -291,9 +185,11 @@ int run(Ctx& c, const l4p_dpt_cfg* cfg, const void* const* hooks, float* out) {
         Vol h1u = c.resize(h1, cfg->out_t, cfg->out_h, cfg->out_w);
         h2 = c.conv3(h1u, "head2.w", "head2.b", cfg->last_dim, one, ACT_RELU, nullptr, nullptr, nullptr);
     }
-    if (c.rc || c.dry) return c.rc;
-    return launch_head_out(c.dt, h2.p, (const float*)c.W("out.w"), (const float*)c.W("out.b"), out,
-                           (long long)h2.t * h2.h * h2.w, c.B, cfg->last_dim, cfg->out_ch, cfg->post_exp, c.st);
+    c.launch([&] {
+        return launch_head_out(c.dt, h2.p, c.Wf("out.w"), c.Wf("out.b"), out, (long long)h2.t * h2.h * h2.w, c.B, cfg->last_dim,
+                               cfg->out_ch, cfg->post_exp, c.st);
+    });
+    return c.rc;
 }
 
 }  // namespace
@@ -302,17 +198,10 @@ extern "C" {
 
 size_t l4p_dpt_workspace_bytes(const l4p_engine* e, const l4p_dpt_cfg* cfg, int B) {
     if (!e || !cfg || B <= 0) return 0;
-    Ctx c;
-    c.e = e;
-    c.st = nullptr;
-    c.dt = e->dtype;
-    c.es = esize_of(e->dtype);
-    c.B = B;
-    c.ws = Bump{nullptr, 0, 0, true};
-    c.dry = true;
-    const void* hooks[4] = {(void*)1, (void*)1, (void*)1, (void*)1};
+    Ctx c(e, B);
+    const void* hooks[4] = {nullptr, nullptr, nullptr, nullptr};
     run(c, cfg, hooks, nullptr);
-    return c.ws.off + 256;
+    return c.ws.bytes_needed();
 }
 
 int l4p_dpt_forward(l4p_engine* e, l4p_stream stream, const char* task, const l4p_dpt_cfg* cfg, const void* const* hooks, int B,
@@ -321,14 +210,8 @@ int l4p_dpt_forward(l4p_engine* e, l4p_stream stream, const char* task, const l4
         l4p_set_error("l4p_dpt_forward: bad arguments");
         return L4P_E_INVALID;
     }
-    Ctx c;
-    c.e = e;
-    c.st = (hipStream_t)stream;
-    c.dt = e->dtype;
-    c.es = esize_of(e->dtype);
-    c.B = B;
-    c.ws = Bump{(char*)workspace, 0, ws_bytes, false};
-    c.pre = std::string("dpt.") + task + ".";
+    Ctx c(e, B, std::string("dpt.") + task + ".");
+    c.on(stream, workspace, ws_bytes);
     return run(c, cfg, hooks, out);
 }
 }

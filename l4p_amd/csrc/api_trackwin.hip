@@ -8,104 +8,36 @@
 // host issues one call per clip and window instead of ~125 ctypes calls with their tensor allocations — with 8 ranks
 // sharing one host's cores that is what keeps the step from becoming launch-bound.
 // The workspace size (l4p_track_window_workspace_bytes) is a dry run of the same function and so depends on the tracker knobs; a
-// workspace that is too small for the current setting is refused (Stack::take returns null, TW::alloc sets L4P_E_INVALID and every
-// launch is behind !rc), never overrun.
+// workspace that is too small for the current setting is refused (graph.hpp: Stack::take returns null, Graph::alloc sets
+// L4P_E_INVALID and every launch is behind Graph::launch), never overrun.
 #include <stdlib.h>
-#include <string.h>
 
-#include <string>
-
-#include "engine.hpp"
+#include "graph.hpp"
 
 namespace {
 
-struct Stack {  // bump allocator with LIFO release (mark / release) and a high-water mark for the size query
-    char* base;
-    size_t off, cap, peak;
-    bool dry;
-    void* take(size_t bytes) {
-        const size_t a = (off + 255) & ~(size_t)255;
-        off = a + bytes;
-        if (off > peak) peak = off;
-        return dry ? (void*)256 : (off <= cap ? base + a : nullptr);
-    }
-};
-
-struct TW {
-    const l4p_engine* e;
-    hipStream_t st;
-    int dt, es;
-    Stack ws;
-    int rc = 0;
-    bool dry = false;
-
-    const void* W(const std::string& k) {
-        if (dry) return (const void*)256;
-        const void* p = e->find("trk." + k);
-        if (!p && !rc) {
-            l4p_set_error("weight 'trk.%s' was never bound", k.c_str());
-            rc = L4P_E_MISSING;
-        }
-        return p;
-    }
-    const float* Wf(const std::string& k) { return (const float*)W(k); }
-    void* alloc(size_t bytes) {
-        void* p = ws.take(bytes);
-        if (!p && !rc) {
-            l4p_set_error("l4p_track_window_forward: workspace too small");
-            rc = L4P_E_INVALID;
-        }
-        return p;
-    }
-    float* f32(long long rows, int cols) { return (float*)alloc((size_t)rows * cols * 4); }
-    void* T(long long rows, int cols) { return alloc((size_t)rows * cols * es); }
+struct TW : Graph {
+    explicit TW(const l4p_engine* e_) : Graph(e_, "l4p_track_window_forward", "trk.") {}
+    using Graph::gemm;
 
     // out = act(a[M][K] (row stride lda) @ w[n][K]^T + bias) (+ res1, float) -> out_T and / or out_f32, row stride ldc
     void gemm(const void* a, long long M, int K, long long lda, const std::string& wk, int n, bool bias, int act, const float* res1,
               int res_mod, float* out_f32, void* out_T, long long ldc, const int* a_map = nullptr, const int* c_map = nullptr) {
-        if (rc || dry) return;
-        GemmParams p = desc(a, M, K, lda, wk, n, bias, act, res1, res_mod, out_f32, out_T, ldc, a_map, c_map);
-        if (!rc) rc = launch_gemm(dt, 0, p, st);
+        gemm(0, desc(a, M, K, lda, wk, n, bias, act, res1, res_mod, out_f32, out_T, ldc, a_map, c_map));
     }
     // several INDEPENDENT projections as one launch (l4p_gemm_group: bit-identical to separate launches)
     void group(const GemmParams* d, int n) {
-        if (rc || dry) return;
-        rc = launch_gemm_group(dt, d, n, st);
+        launch([&] { return launch_gemm_group(dt, d, n, st); });
     }
     GemmParams desc(const void* a, long long M, int K, long long lda, const std::string& wk, int n, bool bias, int act, const float* res1,
                     int res_mod, float* out_f32, void* out_T, long long ldc, const int* a_map = nullptr, const int* c_map = nullptr) {
-        GemmParams p;
-        memset(&p, 0, sizeof(p));
-        if (dry) return p;
-        p.A = a;
-        p.lda = lda;
-        p.W = W(wk + ".w");
-        p.ldw = K;
-        p.M = (int)M;
-        p.N = n;
-        p.K = K;
+        GemmParams p = dense(a, M, K, lda, W(wk + ".w"), K, n);
         p.bias = bias ? Wf(wk + ".b") : nullptr;
         p.act = act;
-        if (res1) {
-            p.res1 = res1;
-            p.res_f32 = 1;
-            p.ldr = n;
-            p.res_mod = res_mod;
-        }
-        p.out_f32 = out_f32;
-        p.out_T = out_T;
-        p.ldc = ldc;
-        p.epi = EPI_DENSE;
-        if (a_map) {
-            p.a_gr = a_map[0];
-            p.a_gs = a_map[1];
-            p.a_go = a_map[2];
-        }
-        if (c_map) {
-            p.c_gr = c_map[0];
-            p.c_gs = c_map[1];
-            p.c_go = c_map[2];
-        }
+        if (res1) p.res1 = res1, p.res_f32 = 1, p.ldr = n, p.res_mod = res_mod;
+        p.out_f32 = out_f32, p.out_T = out_T, p.ldc = ldc;
+        if (a_map) p.a_gr = a_map[0], p.a_gs = a_map[1], p.a_go = a_map[2];
+        if (c_map) p.c_gr = c_map[0], p.c_gs = c_map[1], p.c_go = c_map[2];
         return p;
     }
     // x[M][K] T -> new T [M][n] = act(x W^T + b)
@@ -117,12 +49,11 @@ struct TW {
     // LayerNorm with the tracker's extras (see l4p_layernorm_ex)
     void ln(const float* x32, const std::string& key, float eps, void* oT, float* o32, long long M, int Cc, const float* add,
             int add_mod, void* oT2, int act) {
-        if (rc || dry) return;
-        rc = launch_layernorm_ex(dt, x32, Wf(key + ".g"), Wf(key + ".b"), eps, oT, o32, (int)M, Cc, add, add_mod, oT2, act, st);
+        const float *g = Wf(key + ".g"), *b = Wf(key + ".b");
+        launch([&] { return launch_layernorm_ex(dt, x32, g, b, eps, oT, o32, (int)M, Cc, add, add_mod, oT2, act, st); });
     }
     void attn(int kind, const void* q, const void* k, const void* v, void* out, int N, int P, int D, int heads) {
-        if (rc || dry) return;
-        rc = launch_small_attn(dt, kind, q, k, v, out, N, P, D, heads, st);
+        launch([&] { return launch_small_attn(dt, kind, q, k, v, out, N, P, D, heads, st); });
     }
 };
 
@@ -151,18 +82,16 @@ int run(TW& c, const l4p_track_cfg& g, const float* enc_last, float* hist, const
         const int m1[3] = {half, P, 0}, m2[3] = {half, P, half};
         c.gemm(x, (long long)N * half, Cc, Cc, wk, n, true, ACT_NONE, nullptr, 0, nullptr, o, n, m1, m1);
         c.gemm(x, half, Cc, Cc, wk, n, true, ACT_NONE, nullptr, 0, nullptr, o, n, m2, m2);
-        if (!c.rc && !c.dry)
-            c.rc = launch_broadcast_block(o, (long long)half * n * c.es, (long long)half * n * c.es, (long long)P * n * c.es, N, c.st);
+        c.launch([&] { return launch_broadcast_block(o, (long long)half * n * c.es, (long long)half * n * c.es, (long long)P * n * c.es, N, c.st); });
         return o;
     };
     // ---- prompt tokens (prompt_encoder.py:78-121,196-203; mask_decoder.py:107-113) ----
     float* tok32 = c.f32(6ll * N, Cc);
     void* tokT = c.T(6ll * N, Cc);
-    if (!c.rc && !c.dry) {
-        c.rc = launch_track_tokens(q_off, labels, pfeat, plabel, c.Wf("gauss"), c.Wf("mask_tokens"), c.Wf("point_emb0"),
-                                   c.Wf("point_emb1"), c.Wf("not_a_point"), c.Wf("feat_emb0"), c.Wf("feat_emb1"), tok32, N, Cc, T, H, W,
-                                   c.st, c.dt, tokT);  // (both forms of the tokens from one launch: the values l4p_cast gives)
-    }
+    c.launch([&] {  // (both forms of the tokens from one launch: the values l4p_cast gives)
+        return launch_track_tokens(q_off, labels, pfeat, plabel, c.Wf("gauss"), c.Wf("mask_tokens"), c.Wf("point_emb0"), c.Wf("point_emb1"),
+                                   c.Wf("not_a_point"), c.Wf("feat_emb0"), c.Wf("feat_emb1"), tok32, N, Cc, T, H, W, c.st, c.dt, tokT);
+    });
     // ---- keys = enc_features[-1] + history (sparse_heads.py:341-346); one shared [P][C] set while every track still has
     //      the same history rows (first window), the per-track set from the first image -> token update on ----
     const float* pos = c.Wf("dense_pe");
@@ -181,9 +110,10 @@ int run(TW& c, const l4p_track_cfg& g, const float* enc_last, float* hist, const
     // half_shared: rows [P/2, P) are formed for track 0 only (proj_half_shared reads no others); their float master, which the
     // first layer's "keys = norm4(keys + ...)" needs for every track, lives in kh32 (that LayerNorm runs in place over k32)
     float* kh32 = half_shared ? c.f32(P / 2, Cc) : nullptr;
-    if (!c.rc && !c.dry)
-        c.rc = launch_track_keys_init(c.dt, enc_last, hist, pos, start_shared ? ks32 : k32, start_shared ? ksT : kT,
+    c.launch([&] {
+        return launch_track_keys_init(c.dt, enc_last, hist, pos, start_shared ? ks32 : k32, start_shared ? ksT : kT,
                                       start_shared ? ksP : kP, Nk, P, Cc, half_shared ? P / 2 : 0, kh32, c.st);
+    });
     float* cur32 = start_shared ? ks32 : k32;  // the key set the next projection reads
     void* curT = start_shared ? ksT : kT;
     void* curP = start_shared ? ksP : kP;
@@ -222,32 +152,30 @@ int run(TW& c, const l4p_track_cfg& g, const float* enc_last, float* hist, const
     const int kw_cols = kwin_env && Cc % 128 == 0 ? Cc : 0, kw_len = Dh / g.sam_heads;
     // hs: rows [P/2, P) of keysP / keysT exist for track 0 only (a later window's layer 0): the scores of the two halves are two
     // row-mapped launches, the context product reads those rows from track 0, the projected values (fold_v off) are formed once and copied
+    // scores = keysP x folded^T for every track against its own folded rows (row-grouped weights: a track's P key rows meet that
+    // track's ns folded rows).  hs: rows [P/2, P) of keysP exist for track 0 only - two row-mapped launches over the half blocks
+    auto scores = [&](const void* keysP, const void* folded, int ns, float* sc, bool hs, bool common_keys = false) {
+        GemmParams p = dense(keysP, NP, Cc, Cc, folded, Cc, ns);
+        p.out_f32 = sc, p.ldc = ns;
+        p.w_gr = P, p.w_gs = (long long)ns * Cc, p.b_gs = 0;
+        if (common_keys) p.a_gr = P, p.a_gs = 0, p.a_go = 0;  // every track reads the common key rows
+        if (hs) {
+            const int half = P / 2;
+            p.M = N * half, p.w_gr = half;
+            p.a_gr = half, p.a_gs = P, p.a_go = 0, p.c_gr = half, p.c_gs = P, p.c_go = 0;  // first halves: every track's own
+            c.gemm(0, p);
+            p.a_gs = 0, p.a_go = half, p.c_go = half;                                      // second halves: track 0's rows
+        }
+        c.gemm(0, p);
+    };
     auto t2i_folded = [&](const void* tq, const std::string& prefix, const void* keysP, const void* keysT, void* ta, bool hs) {
         const long long KW = (long long)g.sam_heads * Cc;
         void* qf = c.T((long long)N * HTk + 128, Cc);  // Q' [N][HT][C] (+ slack rows under the last tile)
-        if (!c.rc && !c.dry) {
-            GemmParams pq = c.desc(tq, 6ll * N, Dh, Dh, prefix + ".kfold", (int)KW, false, ACT_NONE, nullptr, 0, nullptr, qf, KW);
-            pq.kw_cols = kw_cols, pq.kw_len = kw_len;
-            if (!c.rc) c.rc = launch_gemm(c.dt, 0, pq, c.st);
-        }
+        GemmParams pq = c.desc(tq, 6ll * N, Dh, Dh, prefix + ".kfold", (int)KW, false, ACT_NONE, nullptr, 0, nullptr, qf, KW);
+        pq.kw_cols = kw_cols, pq.kw_len = kw_len;
+        c.gemm(0, pq);
         float* sc = c.f32(NP, HTk);
-        if (!c.rc && !c.dry) {
-            GemmParams p;
-            memset(&p, 0, sizeof(p));
-            p.A = keysP, p.lda = Cc, p.W = qf, p.ldw = Cc, p.M = (int)NP, p.N = HTk, p.K = Cc;
-            p.out_f32 = sc, p.ldc = HTk, p.epi = EPI_DENSE;
-            p.w_gr = P, p.w_gs = (long long)HTk * Cc, p.b_gs = 0;
-            if (hs) {
-                const int half = P / 2;
-                p.M = N * half, p.w_gr = half;
-                p.a_gr = half, p.a_gs = P, p.a_go = 0, p.c_gr = half, p.c_gs = P, p.c_go = 0;  // first halves: every track's own
-                c.rc = launch_gemm(c.dt, 0, p, c.st);
-                p.a_gs = 0, p.a_go = half, p.c_go = half;                                      // second halves: track 0's rows
-                if (!c.rc) c.rc = launch_gemm(c.dt, 0, p, c.st);
-            } else {
-                c.rc = launch_gemm(c.dt, 0, p, c.st);
-            }
-        }
+        scores(keysP, qf, HTk, sc, hs);
         if (fold_v) {
             const int hd = Dh / g.sam_heads;
             void* pr = c.T(NP, HTk);
@@ -255,17 +183,15 @@ int run(TW& c, const l4p_track_cfg& g, const float* enc_last, float* hist, const
             //  what does matter is that the softmax sums are those of the ROUNDED terms, see t2i_probs_kernel)
             void* cx = c.T((long long)g.sam_heads * RgT, Cc);
             float* stt = c.f32((long long)N * ((P + 255) / 256), 2 * HTk);  // per 256-key split: column maxima, sums
-            if (!c.rc && !c.dry) c.rc = launch_t2i_probs(c.dt, sc, HTk, pr, stt, N, P, HTk, c.st);
-            if (!c.rc && !c.dry) c.rc = launch_t2i_context(c.dt, pr, stt, keysT, cx, N, P, Cc, g.sam_heads, 6, RgT, hs ? P / 2 : P, c.st);
-            if (!c.rc && !c.dry) {
-                GemmParams p = c.desc(cx, (long long)g.sam_heads * RgT, Cc, Cc, prefix + ".v", hd, true, ACT_NONE, nullptr, 0, nullptr, ta, Dh);
-                p.w_gr = (int)RgT, p.w_gs = (long long)hd * Cc, p.b_gs = hd, p.o_gs = hd;
-                p.c_gr = (int)RgT, p.c_gs = 0, p.c_go = 0;
-                if (!c.rc) c.rc = launch_gemm(c.dt, 0, p, c.st);
-            }
+            c.launch([&] { return launch_t2i_probs(c.dt, sc, HTk, pr, stt, N, P, HTk, c.st); });
+            c.launch([&] { return launch_t2i_context(c.dt, pr, stt, keysT, cx, N, P, Cc, g.sam_heads, 6, RgT, hs ? P / 2 : P, c.st); });
+            GemmParams p = c.desc(cx, (long long)g.sam_heads * RgT, Cc, Cc, prefix + ".v", hd, true, ACT_NONE, nullptr, 0, nullptr, ta, Dh);
+            p.w_gr = (int)RgT, p.w_gs = (long long)hd * Cc, p.b_gs = hd, p.o_gs = hd;
+            p.c_gr = (int)RgT, p.c_gs = 0, p.c_go = 0;
+            c.gemm(0, p);
         } else {
             void* tv = hs ? proj_half_shared(keysT, prefix + ".v", Dh) : c.proj(keysT, NP, Cc, prefix + ".v", Dh);
-            if (!c.rc && !c.dry) c.rc = launch_t2i_attn_scores(c.dt, sc, HTk, tv, ta, N, P, Dh, g.sam_heads, c.st);
+            c.launch([&] { return launch_t2i_attn_scores(c.dt, sc, HTk, tv, ta, N, P, Dh, g.sam_heads, c.st); });
         }
     };
     // chained key LayerNorm (see the image -> token block below): L4P_TRACK_LN_CHAIN=0 keeps the float key master
@@ -281,7 +207,7 @@ int run(TW& c, const l4p_track_cfg& g, const float* enc_last, float* hist, const
         const std::string lo = "l" + std::to_string(l) + ".";
         const bool shared = Nk == 1 && N > 1;  // keys still common to all tracks (only in layer 0 of a first window)
         // --- self attention of the prompt tokens (transformer.py:159-166) ---
-        const size_t mark_self = c.ws.off;
+        const size_t mark_self = c.ws.mark();
         {
             void *sq = c.T(6ll * N, Cc), *sk = c.T(6ll * N, Cc), *sv = c.T(6ll * N, Cc);
             const GemmParams qkv[3] = {
@@ -293,10 +219,10 @@ int run(TW& c, const l4p_track_cfg& g, const float* enc_last, float* hist, const
             c.attn(0, sq, sk, sv, sa, N, 6, Cc, g.sam_heads);
             c.gemm(sa, 6ll * N, Cc, Cc, lo + "self.out", Cc, true, ACT_NONE, q32, 0, x32, nullptr, Cc);
         }
-        c.ws.off = mark_self;
+        c.ws.release(mark_self);
         ln_tokens(lo + "norm1");
         // --- tokens -> image (transformer.py:168-173) ---
-        size_t mark = c.ws.off;
+        size_t mark = c.ws.mark();
         {
             void* tq = c.proj(qP, 6ll * N, Cc, lo + "t2i.q", Dh);
             const bool hs = half_shared && l == 0;
@@ -314,18 +240,18 @@ int run(TW& c, const l4p_track_cfg& g, const float* enc_last, float* hist, const
             }
             c.gemm(ta, 6ll * N, Dh, Dh, lo + "t2i.out", Cc, true, ACT_NONE, q32, 0, x32, nullptr, Cc);
         }
-        c.ws.off = mark;
+        c.ws.release(mark);
         ln_tokens(lo + "norm2");
         // --- MLP (transformer.py:175-178), ReLU ---
-        mark = c.ws.off;
+        mark = c.ws.mark();
         {
             void* hdn = c.proj(qT, 6ll * N, Cc, lo + "mlp1", g.sam_mlp, ACT_RELU);
             c.gemm(hdn, 6ll * N, g.sam_mlp, g.sam_mlp, lo + "mlp2", Cc, true, ACT_NONE, q32, 0, x32, nullptr, Cc);
         }
-        c.ws.off = mark;
+        c.ws.release(mark);
         ln_tokens(lo + "norm3");
         // --- image -> tokens (transformer.py:180-185): keys are updated in place ---
-        mark = c.ws.off;
+        mark = c.ws.mark();
         {
             void *ik = c.T(6ll * N, Dh), *iv = c.T(6ll * N, Dh);
             const GemmParams kv[2] = {c.desc(qP, 6ll * N, Cc, Cc, lo + "i2t.k", Dh, true, ACT_NONE, nullptr, 0, nullptr, ik, Dh),
@@ -372,40 +298,21 @@ int run(TW& c, const l4p_track_cfg& g, const float* enc_last, float* hist, const
                 tk[0].kw_cols = tk[1].kw_cols = kw_cols;
                 tk[0].kw_len = tk[1].kw_len = kw_len;
                 c.group(tk, 3);
-                if (pair && !c.rc && !c.dry) c.rc = launch_split_hilo(c.dt, kf32, kf, N, HT, Cc, c.st);
-                if (!c.rc && !c.dry) c.rc = launch_transpose_pad(c.dt, vf, vt, N, HT, Cc, HTp, c.st);
+                if (pair) c.launch([&] { return launch_split_hilo(c.dt, kf32, kf, N, HT, Cc, c.st); });
+                c.launch([&] { return launch_transpose_pad(c.dt, vf, vt, N, HT, Cc, HTp, c.st); });
                 float* sc = c.f32(NP, NS);
                 void* pr = c.T(NP, HTp);
-                if (!c.rc && !c.dry) {
-                    GemmParams p;
-                    memset(&p, 0, sizeof(p));
-                    p.A = curP, p.lda = Cc, p.W = kf, p.ldw = Cc, p.M = (int)NP, p.N = NS, p.K = Cc;
-                    p.out_f32 = sc, p.ldc = NS, p.epi = EPI_DENSE;
-                    p.w_gr = P, p.w_gs = (long long)NS * Cc, p.b_gs = 0;
-                    if (shared) {
-                        p.a_gr = P, p.a_gs = 0, p.a_go = 0;  // every track reads the common key rows
-                        c.rc = launch_gemm(c.dt, 0, p, c.st);
-                    } else if (hs0) {
-                        const int half = P / 2;
-                        p.M = N * half, p.w_gr = half;
-                        p.a_gr = half, p.a_gs = P, p.a_go = 0, p.c_gr = half, p.c_gs = P, p.c_go = 0;  // first halves: every track's own
-                        c.rc = launch_gemm(c.dt, 0, p, c.st);
-                        p.a_gs = 0, p.a_go = half, p.c_go = half;                                      // second halves: track 0's rows
-                        if (!c.rc) c.rc = launch_gemm(c.dt, 0, p, c.st);
-                    } else {
-                        c.rc = launch_gemm(c.dt, 0, p, c.st);
-                    }
-                    if (!c.rc) c.rc = launch_i2t_probs(c.dt, sc, NS, pair ? 1 : 0, cf, P, pr, HTp, NP, g.sam_heads, 6, c.st);
-                    if (!c.rc && delta_env && is16(c.dt) && HTp == 64 && Cc % 128 == 0 && P % 16 == 0) {
-                        // (its own streaming kernel, bit-identical to the GEMM below: see i2t_delta_kernel)
-                        c.rc = launch_i2t_delta(c.dt, pr, vt, c.Wf(lo + "i2t.out.b"), delta, N, P, Cc, HTp, c.st);
-                    } else if (!c.rc) {
-                        memset(&p, 0, sizeof(p));
-                        p.A = pr, p.lda = HTp, p.W = vt, p.ldw = HTp, p.M = (int)NP, p.N = Cc, p.K = HTp;
-                        p.bias = c.Wf(lo + "i2t.out.b"), p.out_T = delta, p.ldc = Cc, p.epi = EPI_DENSE;
-                        p.w_gr = P, p.w_gs = (long long)Cc * HTp, p.b_gs = 0;
-                        c.rc = launch_gemm(c.dt, 0, p, c.st);
-                    }
+                scores(curP, kf, NS, sc, hs0, shared);
+                c.launch([&] { return launch_i2t_probs(c.dt, sc, NS, pair ? 1 : 0, cf, P, pr, HTp, NP, g.sam_heads, 6, c.st); });
+                const float* out_b = c.Wf(lo + "i2t.out.b");
+                if (delta_env && is16(c.dt) && HTp == 64 && Cc % 128 == 0 && P % 16 == 0) {
+                    // (its own streaming kernel, bit-identical to the GEMM below: see i2t_delta_kernel)
+                    c.launch([&] { return launch_i2t_delta(c.dt, pr, vt, out_b, delta, N, P, Cc, HTp, c.st); });
+                } else {
+                    GemmParams p = dense(pr, NP, HTp, HTp, vt, HTp, Cc);
+                    p.bias = out_b, p.out_T = delta, p.ldc = Cc;
+                    p.w_gr = P, p.w_gs = (long long)Cc * HTp, p.b_gs = 0;
+                    c.gemm(0, p);
                 }
             } else {
                 void* iq = half_shared && l == 0 ? proj_half_shared(curP, lo + "i2t.q", Dh)
@@ -416,15 +323,19 @@ int run(TW& c, const l4p_track_cfg& g, const float* enc_last, float* hist, const
             }
             // (after the last layer nothing adds to the float keys any more: only the T copies are written)
             float* o32 = l + 1 < g.sam_depth && !chain_next ? k32 : nullptr;
+            const float *n4g = c.Wf(lo + "norm4.g"), *n4b = c.Wf(lo + "norm4.b");
             if (chained) {  // (the previous layer left its update in k32's storage and its statistics in chain_stats)
-                if (!c.rc && !c.dry)
-                    c.rc = launch_layernorm_chain(c.dt, ks32, P, k32, chain_stats, c.Wf(chain_norm + ".g"), c.Wf(chain_norm + ".b"), delta,
-                                                  c.Wf(lo + "norm4.g"), c.Wf(lo + "norm4.b"), 1e-5f, kT, l + 1 < g.sam_depth ? kc32 : nullptr,
-                                                  (int)NP, Cc, pos, P, kP, c.st);
-            } else if (!c.rc && !c.dry) {
-                c.rc = launch_layernorm_res(c.dt, cur32, shared ? P : 0, delta, c.Wf(lo + "norm4.g"), c.Wf(lo + "norm4.b"), 1e-5f, kT, o32,
-                                            (int)NP, Cc, pos, P, kP, half_shared && l == 0 ? kh32 : nullptr, P, P / 2, c.st, nullptr, nullptr, 0,
-                                            nullptr, chain_next ? chain_stats : nullptr);
+                const float *pg = c.Wf(chain_norm + ".g"), *pb = c.Wf(chain_norm + ".b");
+                c.launch([&] {
+                    return launch_layernorm_chain(c.dt, ks32, P, k32, chain_stats, pg, pb, delta, n4g, n4b, 1e-5f, kT,
+                                                  l + 1 < g.sam_depth ? kc32 : nullptr, (int)NP, Cc, pos, P, kP, c.st);
+                });
+            } else {
+                c.launch([&] {
+                    return launch_layernorm_res(c.dt, cur32, shared ? P : 0, delta, n4g, n4b, 1e-5f, kT, o32, (int)NP, Cc, pos, P, kP,
+                                                half_shared && l == 0 ? kh32 : nullptr, P, P / 2, c.st, nullptr, nullptr, 0, nullptr,
+                                                chain_next ? chain_stats : nullptr);
+                });
             }
             if (chained) cur32_after_chain = kc32;
             chained = chain_next;
@@ -437,10 +348,10 @@ int run(TW& c, const l4p_track_cfg& g, const float* enc_last, float* hist, const
             cur32 = cur32_after_chain ? cur32_after_chain : k32;
             cur32_after_chain = nullptr;
         }
-        c.ws.off = mark;
+        c.ws.release(mark);
     }
     // --- final tokens -> image attention (transformer.py:103-109) ---
-    size_t mark = c.ws.off;
+    size_t mark = c.ws.mark();
     {
         void* fq = c.proj(qP, 6ll * N, Cc, "final.q", Dh);
         void* fa = c.T(RgT, Dh);
@@ -453,19 +364,18 @@ int run(TW& c, const l4p_track_cfg& g, const float* enc_last, float* hist, const
         }
         c.gemm(fa, 6ll * N, Dh, Dh, "final.out", Cc, true, ACT_NONE, q32, 0, x32, nullptr, Cc);
     }
-    c.ws.off = mark;
+    c.ws.release(mark);
     void* hsT = c.T(6ll * N, Cc);
     c.ln(x32, "norm_final", 1e-5f, hsT, x32, 6ll * N, Cc, nullptr, 0, nullptr, ACT_NONE);
 
     // --- hyper-network MLPs on the 3 mask tokens (mask_decoder.py:130-133,160-180) ---
     const int d1 = Cc / g.out_dim_factor, d1p = (d1 + 31) / 32 * 32, cpt = d1p / 32;
     float* hyper = c.f32(3ll * N, d1p);
-    if (!c.rc && !c.dry) {
-        if (hipMemsetAsync(hyper, 0, (size_t)3 * N * d1p * 4, c.st) != hipSuccess) {
-            l4p_set_error("l4p_track_window_forward: hipMemsetAsync failed");
-            c.rc = L4P_E_HIP;
-        }
-    }
+    c.launch([&] {
+        if (hipMemsetAsync(hyper, 0, (size_t)3 * N * d1p * 4, c.st) == hipSuccess) return 0;
+        l4p_set_error("l4p_track_window_forward: hipMemsetAsync failed");
+        return L4P_E_HIP;
+    });
     // (the three tokens' MLPs are independent: each stage of the three runs as one grouped launch; the prompt feature for the
     //  next window (sparse_heads.py:650-658: io token 5) rides with the first stage)
     {
@@ -497,8 +407,7 @@ int run(TW& c, const l4p_track_cfg& g, const float* enc_last, float* hist, const
         c.gemm(curT, (long long)N * half, Cc, Cc, "history_proj", Cc, true, ACT_NONE, nullptr, 0, hist, nullptr, Cc, a_map, c_map);
         // (need_history == 2: the caller guarantees that rows [P/2, P) of every track still hold the mask token - nothing but
         //  this fill ever writes them - so the 0.13 ms pass per 128-query window is skipped)
-        if (!c.rc && !c.dry && need_history != 2)
-            c.rc = launch_fill_rows(hist, c.Wf("history_mask_token"), (long long)N * half, Cc, half, P, half, c.st);
+        if (need_history != 2) c.launch([&] { return launch_fill_rows(hist, c.Wf("history_mask_token"), (long long)N * half, Cc, half, P, half, c.st); });
     }
 
     // --- output up-scaling (mask_decoder.py:58-66,136-137) on channels-last tokens ---
@@ -506,26 +415,16 @@ int run(TW& c, const l4p_track_cfg& g, const float* enc_last, float* hist, const
     const int d0 = (2 * Cc / g.out_dim_factor) < Cc ? 2 * Cc / g.out_dim_factor : Cc;
     const long long M1 = NP * 8;
     void* u0T = c.T(M1, d0);
-    if (!c.rc && !c.dry) {
-        GemmParams p;
-        memset(&p, 0, sizeof(p));
-        p.A = curT;
-        p.lda = Cc;
-        p.W = c.W("up0.w");
-        p.ldw = Cc;
-        p.M = (int)NP;
-        p.N = 8 * d0;
-        p.K = Cc;
-        p.Ti = nt;
-        p.Hi = nh;
-        p.Wi = nw;
+    {
+        GemmParams p = dense(curT, NP, Cc, Cc, c.W("up0.w"), Cc, 8 * d0);
+        p.Ti = nt, p.Hi = nh, p.Wi = nw;
         p.bias = c.Wf("up0.b");
         p.out_T = u0T;
         p.epi = EPI_CONVT;
-        p.kt = p.kh = p.kw = 2;
-        p.Cout = d0;
-        if (!c.rc) c.rc = launch_gemm(c.dt, 0, p, c.st);
-        if (!c.rc) c.rc = launch_layernorm_T(c.dt, u0T, c.Wf("up_ln.g"), c.Wf("up_ln.b"), 1e-6f, u0T, (int)M1, d0, ACT_GELU, c.st);
+        p.kt = p.kh = p.kw = 2, p.Cout = d0;
+        c.gemm(0, p);
+        const float *lg = c.Wf("up_ln.g"), *lb = c.Wf("up_ln.b");
+        c.launch([&] { return launch_layernorm_T(c.dt, u0T, lg, lb, 1e-6f, u0T, (int)M1, d0, ACT_GELU, c.st); });
     }
     // up1 (ConvTranspose (1,2,2) + GELU) fused with the hyper-network mask product (mask_decoder.py:136-139)
     const int Tl = nt * 2, hl = nh * 4, wl = nw * 4;
@@ -535,27 +434,16 @@ int run(TW& c, const l4p_track_cfg& g, const float* enc_last, float* hist, const
     }
     float* partial = (float*)c.alloc((size_t)4 * cpt * 3 * M1 * 4);
     float* masks = (float*)c.alloc((size_t)N * 3 * Tl * hl * wl * 4);
-    if (!c.rc && !c.dry) {
-        GemmParams p;
-        memset(&p, 0, sizeof(p));
-        p.A = u0T;
-        p.lda = d0;
-        p.W = c.W("up1.w");
-        p.ldw = d0;
-        p.M = (int)M1;
-        p.N = 4 * d1p;
-        p.K = d0;
-        p.bias = c.Wf("up1.b");
-        p.act = ACT_GELU;
-        p.out_f32 = partial;
-        p.epi = EPI_MASKDOT;
-        p.Cout = d1p;
-        p.hyper = hyper;
-        p.hyper_rows = (int)(M1 / N);
-        if (!c.rc) c.rc = launch_gemm(c.dt, 0, p, c.st);
-        if (!c.rc) c.rc = launch_mask_gather(partial, masks, N, Tl, nh * 2, nw * 2, cpt, c.st);
-        if (!c.rc) c.rc = launch_track_readout(masks, traj, vis, depth, N, T, hl, wl, H, W, c.st);
-    }
+    GemmParams p = dense(u0T, M1, d0, d0, c.W("up1.w"), d0, 4 * d1p);
+    p.bias = c.Wf("up1.b");
+    p.act = ACT_GELU;
+    p.out_f32 = partial;
+    p.epi = EPI_MASKDOT;
+    p.Cout = d1p;
+    p.hyper = hyper, p.hyper_rows = (int)(M1 / N);
+    c.gemm(0, p);
+    c.launch([&] { return launch_mask_gather(partial, masks, N, Tl, nh * 2, nw * 2, cpt, c.st); });
+    c.launch([&] { return launch_track_readout(masks, traj, vis, depth, N, T, hl, wl, H, W, c.st); });
     return c.rc;
 }
 
@@ -574,15 +462,9 @@ extern "C" {
 
 size_t l4p_track_window_workspace_bytes(const l4p_engine* e, const l4p_track_cfg* cfg, int N, int hist_uniform) {
     if (!e || !cfg_ok(cfg, N)) return 0;
-    TW c;
-    c.e = e;
-    c.st = nullptr;
-    c.dt = e->dtype;
-    c.es = esize_of(e->dtype);
-    c.ws = Stack{nullptr, 0, 0, 0, true};
-    c.dry = true;
+    TW c(e);
     run(c, *cfg, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, N, 1, hist_uniform, nullptr, nullptr, nullptr, nullptr);
-    return c.ws.peak + 256;
+    return c.ws.bytes_needed();
 }
 
 int l4p_track_window_forward(l4p_engine* e, l4p_stream stream, const l4p_track_cfg* cfg, const float* enc_last, float* hist,
@@ -594,13 +476,8 @@ int l4p_track_window_forward(l4p_engine* e, l4p_stream stream, const l4p_track_c
         l4p_set_error("l4p_track_window_forward: null argument");
         return L4P_E_INVALID;
     }
-    TW c;
-    c.e = e;
-    c.st = (hipStream_t)stream;
-    c.dt = e->dtype;
-    c.es = esize_of(e->dtype);
-    const size_t pad = (size_t)(-(uintptr_t)workspace & 255);  // to the next 256-byte boundary
-    c.ws = Stack{(char*)workspace + pad, 0, ws_bytes > pad ? ws_bytes - pad : 0, 0, false};
+    TW c(e);
+    c.on(stream, workspace, ws_bytes);
     return run(c, *cfg, enc_last, hist, q_off, labels, pfeat, plabel, N, need_history, hist_uniform, traj, vis, depth, new_pfeat);
 }
 

@@ -123,10 +123,31 @@ inline long long gemm_tiles(const l4p_gemm_desc& p, int bm, int bn) { return (lo
 // split-K problems (the low-resolution DPT convs, N >= 256): always the wider tile.  With 128x64 tiles four
 // co-resident workgroups per CU pull (128 + 64) x 64 operands per k-tile each and the launch is bound by L2
 // bandwidth (M = 8192, N = 256, K = 27648: 2.65 GB of tile loads in 250 us); 128x128 halves the bytes per FLOP
-// (250 -> 147 us, 77 -> 59 us, 133 -> 92 us on the c3 shapes).  The split count (splitk_for) assumes this.
+// (250 -> 147 us, 77 -> 59 us, 133 -> 92 us on the c3 shapes).  The split count (conv3d_splitk) assumes this.
 inline bool gemm_is_big(const l4p_gemm_desc& p) {
     const long long t128 = gemm_tiles(p, 128, 128);
     return (t128 >= 400 && !(t128 > 512 && t128 < 640)) || (p.splitk > 1 && p.N >= 256);
+}
+
+// Split-K factor of a 3x3x3 conv whose output has too few tiles to occupy 256 CUs while K is long (the low-resolution DPT convs:
+// M = 256..16384 voxels, K = 27*256..27*1024).  A contract between caller and launcher - the caller allocates
+// partial[splitk][M][N] - so it is stated once: the DPT graph calls it, everyone else reaches it as l4p_conv3d_splitk.
+inline int conv3d_splitk(long long M, int N, int K, int esize) {
+    const int nk = (K + 128 / esize - 1) / (128 / esize);
+    if (nk < 32) return 1;
+    long long s;
+    if (N >= 256) {  // 128x128 tiles, two workgroups per CU: aim at 512 workgroups (gemm_is_big picks the tile)
+        const long long tiles = ((M + 127) / 128) * ((N + 127) / 128);
+        if (tiles >= 400) return 1;
+        s = 512 / tiles;
+    } else {  // 128x64 tiles: ~1024 workgroups (4 per CU): one 4-wave workgroup per CU is latency-bound
+        const long long tiles = ((M + 127) / 128) * ((N + 63) / 64);
+        if (tiles >= 512) return 1;
+        s = 1024 / tiles;
+    }
+    if (s > 16) s = 16;
+    if (s > nk / 8) s = nk / 8;
+    return s < 1 ? 1 : (int)s;
 }
 
 // a problem the grouped launch takes: what gemm_select would run on the four-stage 128x64 kernel

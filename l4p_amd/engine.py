@@ -65,13 +65,9 @@ class Engine:
             self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
         return self._ws
 
-    @_on_device
-    def dpt_forward(self, task: str, hooks: Sequence[torch.Tensor], out_ch: int, actpost, fusion,
-                    out_size: Tuple[int, int, int], post_exp: bool) -> torch.Tensor:
-        """DPTOutputAdapter_fix.forward (dpt_head.py:41-86) of head ``task`` as one native call.
-        hooks: 4 x [B, P, C] engine dtype; returns float [B, out_ch, T, H, W]."""
+    def dpt_cfg(self, out_ch: int, actpost, fusion, out_size: Tuple[int, int, int], post_exp: bool) -> "_lib.DptCfg":
+        """The l4p_dpt_cfg of a head of this geometry."""
         c = self.cfg
-        B = hooks[0].shape[0]
         dc = _lib.DptCfg()
         dc.dim = c.dim
         dc.nt, dc.nh, dc.nw = c.grid
@@ -83,6 +79,15 @@ class Engine:
         dc.feature_dim, dc.last_dim, dc.out_ch = c.feature_dim, c.last_dim, out_ch
         dc.out_t, dc.out_h, dc.out_w = out_size
         dc.post_exp = 1 if post_exp else 0
+        return dc
+
+    @_on_device
+    def dpt_forward(self, task: str, hooks: Sequence[torch.Tensor], out_ch: int, actpost, fusion,
+                    out_size: Tuple[int, int, int], post_exp: bool) -> torch.Tensor:
+        """DPTOutputAdapter_fix.forward (dpt_head.py:41-86) of head ``task`` as one native call.
+        hooks: 4 x [B, P, C] engine dtype; returns float [B, out_ch, T, H, W]."""
+        B = hooks[0].shape[0]
+        dc = self.dpt_cfg(out_ch, actpost, fusion, out_size, post_exp)
         key = (task, B)
         ws = self._dpt_ws.get(key)
         if ws is None:

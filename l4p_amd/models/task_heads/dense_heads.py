@@ -1,24 +1,21 @@
 """Dense DPT heads on the MI355X engine — host mirror of l4p/models/task_heads/dense_heads.py.
 
 Same class names, constructor arguments, ``forward`` / ``forward_windowed`` signatures and output keys
-as the reference; the arithmetic runs in libl4p_hip.so through l4p_amd.ops (channels-last tensors,
-implicit-GEMM 3x3x3 convs, ConvTranspose-as-GEMM, fused ReLU / bias / skip epilogues).
+as the reference; the decoder runs in libl4p_hip.so as one native call per head (l4p_dpt_forward:
+channels-last tensors, implicit-GEMM 3x3x3 convs, ConvTranspose-as-GEMM, fused ReLU / bias / skip
+epilogues).  csrc/api_dpt.hip is the one statement of that graph.
 
-One algebraic re-ordering versus the reference graph: FeatureFusionBlock's ``out_conv`` (a 1x1x1 conv)
-is applied BEFORE the trilinear up-sampling instead of after it (dpt_block.py:229-237).  Both are
-linear and the interpolation weights sum to one, so the result is identical up to float rounding,
-while the conv runs on 2-8x fewer voxels.
+One algebraic re-ordering versus the reference graph (csrc/api_dpt.hip, run()): FeatureFusionBlock's
+``out_conv`` (a 1x1x1 conv) is applied BEFORE the trilinear up-sampling instead of after it
+(dpt_block.py:229-237).  Both are linear and the interpolation weights sum to one, so the result is
+identical up to float rounding, while the conv runs on 2-8x fewer voxels.
 """
 from __future__ import annotations
 
-import os
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from ... import ops
-from ... import _lib
-from ..._lib import ACT_NONE, ACT_RELU
 from ...weights import ModelCfg, actpost_of, fusion_of
 from ..aligner import LstSqAffineAligner, LinearAligner, WindowOverlapAligner
 
@@ -28,70 +25,6 @@ class _Runtime:
 
     def __init__(self, cfg: ModelCfg, weights, dtype: int):
         self.cfg, self.weights, self.dtype = cfg, weights, dtype
-
-
-def _conv_rcu(W, key: str, x: torch.Tensor, x_relu: torch.Tensor, feat: int, extra: Optional[torch.Tensor] = None,
-              relu_copy: bool = False):
-    """ResidualConvUnit_custom (dpt_block.py:131-157): conv2(relu(conv1(relu(x)))) + x  [+ extra].
-    relu(x) comes pre-computed from the epilogue of the kernel that produced x (so conv1 streams its input by
-    LDS-DMA); conv1's own ReLU is an output activation; the skip adds ride conv2's epilogue."""
-    y = ops.conv3d_k3(x_relu, W[key + ".c1.w"], feat, bias=W[key + ".c1.b"], act=ACT_RELU)
-    return ops.conv3d_k3(y, W[key + ".c2.w"], feat, bias=W[key + ".c2.b"], res1=x, res2=extra, relu_copy=relu_copy)
-
-
-def dpt_decode(W, cfg: ModelCfg, task: str, hooks: Sequence[torch.Tensor], out_ch: int,
-               output_size: Optional[Tuple[int, int, int]], image_size: Tuple[int, int, int], post_exp: bool) -> torch.Tensor:
-    """DPTOutputAdapter_fix.forward (dpt_head.py:41-86) on channels-last device tensors.
-    hooks: 4 x [B, P, C] engine-dtype features of layers cfg.hooks.  Returns float [B, out_ch, T, H, W]."""
-    pre = f"dpt.{task}."
-    Wt = lambda k: W[pre + k]
-    nt, nh, nw = cfg.grid
-    B = hooks[0].shape[0]
-    F_ = cfg.feature_dim
-    ap, fu = actpost_of(task), fusion_of(task)
-    layers: List[torch.Tensor] = []
-    for i in range(4):
-        Li = cfg.layer_dims[i]
-        a, _ = ops.gemm(hooks[i].reshape(B * cfg.tokens, cfg.dim), Wt(f"act{i}.0.w"), Li, bias=Wt(f"act{i}.0.b"))
-        a = a.view(B, nt, nh, nw, Li)
-        sf = ap[i]
-        if any(s > 0 for s in sf):
-            k = tuple(2 ** s for s in sf)
-            # knob dpt_fold_rn (csrc/api_dpt.hip, fold_fits): ConvTranspose + rn as one sub-pixel conv where the folded weights exist
-            kv = _lib.load().l4p_get_knob(b"dpt_fold_rn")
-            if (kv and (kv >= 2 or k[0] * k[1] * k[2] >= 8) and pre + f"fold{i}.w" in W and pre + f"fold{i}.b" in W
-                    and Li % (128 // a.element_size()) == 0 and F_ % 128 == 0 and k[0] * k[1] * k[2] <= 64
-                    and nt * k[0] >= 2 and nh * k[1] >= 2 and nw * k[2] >= 2):
-                layers.append(ops.conv3d_subpixel(a, Wt(f"fold{i}.w"), F_, k, bias_cls=Wt(f"fold{i}.b"), relu_copy=True))
-                continue
-            a = ops.conv_transpose(a, Wt(f"act{i}.1.w"), Li, tuple(2 ** s for s in sf), bias_taps=Wt(f"act{i}.1.b"))
-        elif any(s < 0 for s in sf):
-            a = ops.conv3d_k3(a, Wt(f"act{i}.1.w"), Li, stride=tuple(2 ** (-s) for s in sf), bias=Wt(f"act{i}.1.b"))
-        layers.append(ops.conv3d_k3(a, Wt(f"rn{i}.w"), F_, relu_copy=True))  # (x, relu(x))
-
-    def fuse(r: int, x0, x1, scale: Sequence[int]) -> torch.Tensor:
-        key = f"{pre}ref{r}"
-        if x1 is not None:
-            out, out_relu = _conv_rcu(W, key + ".rcu1", x1[0], x1[1], F_, extra=x0, relu_copy=True)  # x0 + RCU1(x1)
-        else:
-            out, out_relu = x0
-        out = _conv_rcu(W, key + ".rcu2", out, out_relu, F_)
-        b_, t_, h_, w_, _ = out.shape
-        o, _ = ops.gemm(out.view(-1, F_), W[key + ".out.w"], F_, bias=W[key + ".out.b"])
-        o = o.view(b_, t_, h_, w_, F_)
-        return ops.upsample_trilinear(o, (t_ * scale[0], h_ * scale[1], w_ * scale[2]), align_corners=True)
-
-    p4 = fuse(4, layers[3], None, fu[3])
-    if p4.shape[1] != layers[2][0].shape[1] or p4.shape[2] != layers[2][0].shape[2]:
-        p4 = p4[:, : layers[2][0].shape[1], : layers[2][0].shape[2]].contiguous()  # dpt_head.py:70-72
-    p3 = fuse(3, p4, layers[2], fu[2])
-    p2 = fuse(2, p3, layers[1], fu[1])
-    p1 = fuse(1, p2, layers[0], fu[0])
-    h = ops.conv3d_k3(p1, Wt("head1.w"), F_ // 2, bias=Wt("head1.b"))
-    osz = tuple(image_size) if output_size is None else tuple(output_size)
-    h = ops.upsample_trilinear(h, osz, align_corners=True)
-    h = ops.conv3d_k3(h, Wt("head2.w"), cfg.last_dim, bias=Wt("head2.b"), act=ACT_RELU)
-    return ops.head_out(h, Wt("out.w"), Wt("out.b"), post_exp)
 
 
 class VideoMAEFlowDPTHead(torch.nn.Module):
@@ -133,14 +66,10 @@ class VideoMAEFlowDPTHead(torch.nn.Module):
         pre = getattr(enc_features_bpc_list, "decoded", None)
         if pre is not None and self._engine_task in pre:
             return pre[self._engine_task]  # window decoded earlier / on another rank (parallel.DecodedWindow)
-        if self._rt is None:
+        eng = getattr(self._rt, "engine", None)
+        if eng is None:
             raise RuntimeError(f"head '{self.task_name}' has no weights: call load_state_dict on the model first")
         hooks = [enc_features_bpc_list.T(h) for h in self.hooks_idx]
-        eng = getattr(self._rt, "engine", None)
-        if eng is None or os.environ.get("L4P_DPT_PYTHON"):
-            # kernel-by-kernel composition from Python (the readable statement of the graph; same kernels)
-            return dpt_decode(self._rt.weights, self._rt.cfg, self._engine_task, hooks, self.out_nchan, self.output_size,
-                              tuple(img_info), self._post_exp)
         out_ch = self._rt.weights[f"dpt.{self._engine_task}.out.w"].shape[0]
         osz = tuple(img_info) if self.output_size is None else tuple(self.output_size)
         return eng.dpt_forward(self._engine_task, hooks, out_ch, actpost_of(self._engine_task), fusion_of(self._engine_task),

@@ -1,8 +1,9 @@
 """torch.Tensor -> raw pointer plumbing over the kernel-level C ABI (include/l4p_hip.h).
 
 PyTorch is used here only for device memory and the current HIP stream; every FLOP runs in
-libl4p_hip.so.  These wrappers are what tests/ call for per-kernel parity and what the host mirror
-(l4p_amd.models.*) composes.
+libl4p_hip.so.  These wrappers are the kernel-level surface: what tests/ and tools/ call for per-kernel
+parity and measurement.  The model's forward does not come through here: it runs the native graphs
+(l4p_amd.engine: encoder, DPT decoder, tracker window) with one call each.
 """
 from __future__ import annotations
 
@@ -99,26 +100,6 @@ def gemm(a: torch.Tensor, w: torch.Tensor, n: int, *, bias: Optional[torch.Tenso
     return oT, of
 
 
-def splitk_for(M: int, N: int, K: int, es: int) -> int:
-    """Split-K factor for problems whose output has too few tiles to occupy 256 CUs while K is long (the low-resolution
-    DPT convs: M = 256..16384 voxels, K = 27*256..27*1024).  Mirrors csrc/api_dpt.hip:splitk_for: N >= 256 runs on 128x128
-    tiles (512 workgroups aimed at), narrower outputs on 128x64 tiles (1024 workgroups)."""
-    nk = (K + 128 // es - 1) // (128 // es)
-    if nk < 32:
-        return 1
-    if N >= 256:
-        tiles = ((M + 127) // 128) * ((N + 127) // 128)
-        if tiles >= 400:
-            return 1
-        s = 512 // tiles
-    else:
-        tiles = ((M + 127) // 128) * ((N + 63) // 64)
-        if tiles >= 512:
-            return 1
-        s = 1024 // tiles
-    return max(1, min(16, s, nk // 8))
-
-
 def kv_block(dtype: torch.dtype) -> int:
     """Keys per attention KV block (a 128-byte V^T tile row): 64 for bf16, 32 for f32."""
     return 128 // torch.empty((), dtype=dtype).element_size()
@@ -210,11 +191,11 @@ def conv3d_k3(x: torch.Tensor, w: torch.Tensor, cout: int, *, stride: Tuple[int,
         d.ups_hi, d.ups_wi = lo
     out_relu = torch.empty_like(out) if relu_copy else None
     d.out_relu_T = _p(out_relu)
-    sk = splitk_for(d.M, cout, 27 * Cin, x.element_size()) if lo is None else 1
+    lib = _lib.load()
+    sk = lib.l4p_conv3d_splitk(d.M, cout, 27 * Cin, dtype) if lo is None else 1  # (the caller owns the partials: the engine's rule)
     if sk > 1:
         partial = torch.empty((sk, d.M, cout), dtype=torch.float32, device=x.device)
         d.splitk, d.partial = sk, _p(partial)
-    lib = _lib.load()
     _lib.check(lib.l4p_conv3d_k3(_stream(), dtype, C.byref(d)), "l4p_conv3d_k3")
     return (out, out_relu) if relu_copy else out
 

@@ -151,7 +151,7 @@ def mini():
 
 
 @pytest.mark.parametrize("precision,tol_max,tol_l2", [("32-true", 1e-3, 1e-3), ("bf16", None, 3e-2), ("16-mixed", None, 4e-3)])
-def test_decoder_takes_the_folded_form_by_knob(dev, knob, mini, precision, tol_max, tol_l2, monkeypatch):
+def test_decoder_takes_the_folded_form_by_knob(dev, knob, mini, precision, tol_max, tol_l2):
     from tests.golden_utils import make_batch
     from tests.test_encoder_dpt_gpu import build
 
@@ -169,12 +169,6 @@ def test_decoder_takes_the_folded_form_by_knob(dev, knob, mini, precision, tol_m
         with torch.no_grad(), prof_tags() as pt:
             out[v] = model.forward({k: t.clone() for k, t in batch.items()}, tasks)
         tags[v] = pt
-        monkeypatch.setenv("L4P_DPT_PYTHON", "1")  # the Python composition takes the same launches under either setting: bit for bit
-        with torch.no_grad():
-            py = model.forward({k: t.clone() for k, t in batch.items()}, tasks)
-        monkeypatch.delenv("L4P_DPT_PYTHON")
-        for key in keys:
-            assert torch.equal(out[v][key], py[key]), (v, key)
     torch.cuda.synchronize()
     on, off = tags[2], tags[0]
     assert on.count("subpix") == 4 and off.count("subpix") == 0, (on.lines, off.lines)  # levels 0 and 1 of both heads

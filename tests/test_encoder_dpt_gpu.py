@@ -95,21 +95,57 @@ def test_mini_encoder_and_dense_heads_vs_oracle_and_golden(dev, mini, precision,
         assert_bf16_within_reference_drift(drift, "mini_T16_all", precision=precision)
 
 
-@pytest.mark.parametrize("precision", ["32-true", "bf16", "16-mixed"])
-def test_native_dpt_call_equals_python_composition(dev, mini, precision, monkeypatch):
-    """l4p_dpt_forward (one C++ call) issues the same kernels in the same order as dense_heads.dpt_decode
-    (kernel-by-kernel from Python): outputs must be bit-identical, for a full-resolution head and the camray head."""
+def test_dpt_workspace_too_small_is_refused_and_its_size_ignores_the_fold_knob(dev, mini, knob, monkeypatch):
+    """l4p_dpt_forward on a workspace declared half as large as l4p_dpt_workspace_bytes asks: L4P_E_INVALID, "workspace too small"
+    (the pointer is the full buffer: nothing can be overrun whatever the code does); the full-size call on the same buffer then
+    equals the model's own forward bit for bit.  And the size is that of the unfolded form whatever dpt_fold_rn says (the knob may
+    change between sizing and a forward): a full-resolution head and camray."""
+    import ctypes as C
+
+    from l4p_amd import _lib
+    from l4p_amd.weights import actpost_of, fusion_of
+
     cfg, sd = mini
-    model = build(cfg, sd, precision)
+    model = build(cfg, sd, "bf16")
+    heads = model.l4p_model.task_heads
+    eng = heads["depth"]._rt.engine
+    calls = {}
+    real = eng.dpt_forward
+
+    def spy(task, hooks, *args):
+        calls[task] = (hooks, args, real(task, hooks, *args))
+        return calls[task][2]
+
+    monkeypatch.setattr(eng, "dpt_forward", spy)
     batch = make_batch(16, 2)
-    tasks = ["depth", "camray"]
     with torch.no_grad():
-        a = model.forward({k: v.clone() for k, v in batch.items()}, tasks)
-        monkeypatch.setenv("L4P_DPT_PYTHON", "1")
-        b = model.forward({k: v.clone() for k, v in batch.items()}, tasks)
+        fresh = model.forward({k: v.clone() for k, v in batch.items()}, ["depth", "camray"])
     torch.cuda.synchronize()
-    for k in ("depth_est_b1thw", "traj3d_est_b16t"):
-        assert torch.equal(a[k], b[k]), k
+    lib = _lib.load()
+    for task in ("depth", "camray"):
+        hooks, (out_ch, actpost, fusion, osz, post_exp), want = calls[task]
+        assert actpost == actpost_of(task) and fusion == fusion_of(task)
+        B = hooks[0].shape[0]
+        dc = eng.dpt_cfg(out_ch, actpost, fusion, osz, post_exp)
+        sizes, default = {}, int(lib.l4p_get_knob(b"dpt_fold_rn"))
+        for v in (0, 1, 2):
+            knob("dpt_fold_rn", v)
+            sizes[v] = int(lib.l4p_dpt_workspace_bytes(eng.handle, C.byref(dc), B))
+        knob("dpt_fold_rn", default)  # (what the model's forward above ran with)
+        need = sizes[default]
+        assert need > 0 and sizes[0] == need and sizes[2] == need, sizes
+        ws = torch.empty(need, dtype=torch.uint8, device="cuda")
+        hs = [h.contiguous() for h in hooks]
+        hp = (C.c_void_p * 4)(*[h.data_ptr() for h in hs])
+        out = torch.zeros((B, out_ch) + tuple(osz), dtype=torch.float32, device="cuda")
+        args = (eng.handle, torch.cuda.current_stream().cuda_stream, task.encode(), C.byref(dc), hp, B, ws.data_ptr())
+        rc = lib.l4p_dpt_forward(*args, need // 2, out.data_ptr())
+        assert rc == -1 and "workspace too small" in lib.l4p_last_error().decode(), (rc, lib.l4p_last_error())  # L4P_E_INVALID
+        _lib.check(lib.l4p_dpt_forward(*args, need, out.data_ptr()), "l4p_dpt_forward")
+        torch.cuda.synchronize()
+        assert torch.equal(out, want), task
+        if task == "depth":
+            assert torch.equal(out[:, :1], fresh["depth_est_b1thw"])
 
 
 @pytest.mark.parametrize("precision", ["bf16", "16-mixed"])

@@ -46,6 +46,34 @@ def test_abi_header_symbols_are_bound_and_exported():
     assert lib.l4p_prof_num_classes() >= 3
 
 
+# (M, N, K, element size) -> split-K factor, as the rule stood in Python beside its C++ twin before both became l4p_conv3d_splitk
+SPLITK_TABLE = {
+    # the decoder's own shapes
+    (256, 256, 6912, 2): 13, (2048, 256, 13824, 2): 16, (16384, 256, 6912, 2): 2, (8192, 256, 13824, 2): 4,
+    (6400, 256, 13824, 2): 5, (4096, 128, 3456, 2): 6, (32768, 256, 13824, 2): 1, (512, 64, 1728, 2): 1,
+    (4096, 256, 13824, 2): 8, (131072, 256, 6912, 2): 1, (1024, 256, 27648, 2): 16, (512, 1024, 19008, 2): 16,
+    # fewer than 32 k-tiles: none (nk = 31 | 32, 2-byte and 4-byte elements; a ragged last k-tile counts)
+    (256, 256, 1984, 2): 1, (256, 256, 1985, 2): 4, (256, 256, 2048, 2): 4, (256, 256, 992, 4): 1, (256, 256, 1024, 4): 4,
+    # N >= 256, 128x128 tiles: 399, 398 | 400 tiles, and the last count that still splits (256 | 258 tiles)
+    (17024, 384, 6912, 2): 1, (25472, 256, 6912, 2): 1, (25600, 256, 6912, 2): 1, (16384, 256, 13824, 2): 2, (16512, 256, 13824, 2): 1,
+    # N < 256, 128x64 tiles: 511 | 512 tiles, 510 | 512 at N = 128
+    (65408, 64, 13824, 2): 2, (65536, 64, 13824, 2): 1, (32640, 128, 3456, 2): 2, (32768, 128, 3456, 2): 1,
+    # the cap at 16 and the cap at nk / 8; rows that do not fill a tile; 4-byte elements
+    (256, 256, 13824, 2): 16, (128, 256, 27648, 2): 16, (129, 256, 6912, 2): 13, (256, 128, 2048, 2): 4,
+    (8192, 256, 6912, 4): 4, (2048, 256, 13824, 4): 16,
+}
+
+
+def test_conv3d_splitk_rule_against_its_table():
+    """l4p_conv3d_splitk (csrc/gemm_select.hpp conv3d_splitk): the one statement of the split-K rule that l4p_dpt_forward and
+    ops.conv3d_k3 share.  Pure host arithmetic: every branch edge and the decoder's own shapes, as literal numbers."""
+    lib = _lib.load()
+    for (M, N, K, es), want in SPLITK_TABLE.items():
+        for dtype in ((_lib.L4P_BF16, _lib.L4P_F16) if es == 2 else (_lib.L4P_F32,)):
+            assert lib.l4p_conv3d_splitk(M, N, K, dtype) == want, (M, N, K, es, dtype)
+    assert lib.l4p_conv3d_splitk(256, 256, 6912, 7) == 0 and lib.l4p_conv3d_splitk(0, 256, 6912, _lib.L4P_BF16) == 0
+
+
 def test_packing_conv_and_convT_matrices_reproduce_torch_ops():
     g = torch.Generator().manual_seed(0)
     x = torch.randn(1, 8, 3, 4, 5, generator=g)
