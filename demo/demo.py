@@ -15,6 +15,7 @@ free viewpoint) on the GPU, along an orbit camera path, as a video under DIR.
   python demo/demo.py --davis DAVIS_ROOT --ckpt ...    # JPEGImages/480p/<seq>, Annotations/480p/<seq>: queries on the instance masks
   python demo/demo.py --dycheck DYCHECK_ROOT --ckpt ... --recon4d out/   # <seq>/dense/images, <seq>/calibration.txt
   python demo/demo.py --synthetic --davis X --vis out/ # a small seeded DAVIS (or --dycheck: DyCheck) tree in a temporary directory
+  python demo/demo.py --synthetic --frames 32 --bidirectional --query-frame 12 --vis out/   # queries on frame 12, tracked both ways
 
 With --synthetic the weights are the name-seeded random tensors of the test-suite (same 916-key state dict a checkpoint
 holds) and the "video" is l4p_amd.data.synthetic.synthetic_video: the point is the plumbing and the timing, not the pictures.
@@ -62,6 +63,11 @@ def parse_args(argv=None):
     ap.add_argument("--view4d", default=None, metavar="DIR",
                     help="also run the camray task and render each video's 4D reconstruction from an orbiting viewpoint (points, track "
                          "trails, camera frusta; l4p_amd.utils.view4d.generate_4D_video) as <seq_name>_4d under DIR")
+    ap.add_argument("--bidirectional", action="store_true",
+                    help="track every query in both time directions (estimation_directions [1, -1] on the tracker head and the dataset): "
+                         "the frames before a query are estimated by a second tracker pass over the time-flipped clip")
+    ap.add_argument("--query-frame", type=int, default=None, metavar="K",
+                    help="place the sampled queries on frame K (time K + 0.5) instead of frame 0, where the datasets sample them")
     ap.add_argument("--precision", default="16-mixed",
                     help="engine: 16-mixed (the reference demo's own, IEEE half; default) | bf16 (what bench.py measures) | 32-true")
     args = ap.parse_args(argv)
@@ -69,6 +75,8 @@ def parse_args(argv=None):
         ap.error("--videos, --davis and --dycheck are one input each: give one")
     if not args.synthetic and not (args.ckpt and (args.videos or args.davis or args.dycheck)):
         ap.error("--ckpt and one of --videos / --davis / --dycheck (or --synthetic)")
+    if args.query_frame is not None and args.query_frame < 0:
+        ap.error("--query-frame: a frame index >= 0")
     if args.spacing is None:
         args.spacing = 0.02 if args.davis else 0.04  # demo.py:50,133 / :88,221
     return args
@@ -79,7 +87,8 @@ def plan(args):
     tasks = ["depth", "flow_2d_backward", "dyn_mask", "track_2d"]  # demo.py:82,99
     if args.recon4d or args.view4d or args.dycheck:
         tasks.append("camray")  # the reference's 4D sections (demo.py:116-258) add it
-    kw = dict(crop_size=(args.frames, 224, 224), estimation_directions=[1], track_2d_querry_sampling_spacing=args.spacing)
+    kw = dict(crop_size=(args.frames, 224, 224), estimation_directions=[1, -1] if args.bidirectional else [1],
+              track_2d_querry_sampling_spacing=args.spacing)
     if args.davis and (args.recon4d or args.view4d):
         kw["crop_size"] = (56, 224, 224)  # demo.py:131
     if args.dycheck:
@@ -118,6 +127,8 @@ def main(argv=None):
                               precision=precision, accelerator=accelerator)
 
     model.l4p_model.window_batch = 8  # windows of a long clip go through encoder + dense decoders eight at a time
+    if args.bidirectional:
+        model.l4p_model.task_heads["track_2d"].estimation_directions = [1, -1]
     with contextlib.ExitStack() as stack:
         if args.synthetic and (args.davis or args.dycheck):
             root = synthetic_tree(args, stack.enter_context(tempfile.TemporaryDirectory()))
@@ -143,6 +154,10 @@ def main(argv=None):
 def run(args, model, dataset, tasks):
     loader = torch.utils.data.DataLoader(dataset, batch_size=1, shuffle=False)
     for batch in loader:
+        if args.query_frame is not None:
+            if args.query_frame >= batch["rgb_b3thw"].shape[2]:
+                raise SystemExit(f"--query-frame {args.query_frame}: the clip has {batch['rgb_b3thw'].shape[2]} frames")
+            batch["track_2d_pointquerries_bn3"][..., 0] = args.query_frame + 0.5
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         with torch.no_grad():

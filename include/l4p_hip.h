@@ -43,7 +43,8 @@ typedef void* l4p_stream; /* hipStream_t */
 typedef struct l4p_engine l4p_engine;
 
 const char* l4p_last_error(void);
-int l4p_abi_version(void); /* 20: the split-K rule of the 3x3x3 conv, stated once for caller and launcher (l4p_conv3d_splitk);
+int l4p_abi_version(void); /* 21: tracking in both time directions (l4p_time_reverse, l4p_track_bidir_queries, l4p_track_bidir_merge);
+                              * 20: the split-K rule of the 3x3x3 conv, stated once for caller and launcher (l4p_conv3d_splitk);
                               * 19: 3D-track metrics, inverse-depth alignment and log-space depth errors (l4p_metric_tracks3d,
                               * l4p_metric_tracks3d_ws_bytes, l4p_metric_depth_full, l4p_metric_depth_full_ws_bytes);
                               * 18: the L4PDataset base class (l4p_gt_dense_clip, l4p_gt_query_select, l4p_gt_tracks_clip);
@@ -806,6 +807,27 @@ int l4p_track_commit(l4p_stream stream, const float* w_traj, const float* w_vis,
                      const unsigned char* valid_t, const unsigned char* valid_n, float* traj, float* vis, float* depth,
                      int T, int start, int ws, int next_start, int last_window, float* cur_q, float* plabel,
                      const float* new_pfeat, float* pfeat, int* best_out, int N, int C);
+
+/* Tracking in both time directions (estimation_directions [1, -1]).  The reference's recursion is causal - a frame is estimated iff
+ * frame centre - query time >= 0 (sparse_heads.py:306-316) - and its assert names the recipe for the frames before a query
+ * (sparse_heads.py:242-245): "Run twice, with and without video flipping, and then combine outputs".  The reversed pass is the same
+ * recursion on the time-flipped clip (frame f' of it is frame T-1-f' of the input) with the queries ((float)T - tq, x, y); output frame g
+ * of a track is the forward pass's iff ((float)g + 0.5f) - tq >= 0 in f32 (the expression l4p_track_prepare evaluates), else the reversed
+ * pass's at frame T-1-g: traj (both channels), vis and depth alike.  At the query frame the forward value wins.
+ * Each entry returns L4P_E_INVALID, with nothing launched, for a null pointer it needs, a size < 1, or src == dst in the first.
+ *   l4p_time_reverse       : float [outer][T][inner] -> the same shape with the T axis reversed; src != dst.  16-byte accesses when
+ *                            inner % 4 == 0 and both pointers are 16-byte aligned, scalar ones otherwise.  (rgb_b3thw: outer = 3 B, inner = H W)
+ *   l4p_track_bidir_queries: q_rev [BN][3] = the flipped queries; ADDS to the device int need_count (zeroed by the caller) the number of
+ *                            queries with at least one frame before them, (0.5f - tq) < 0: 0 means the reversed pass owns no frame.
+ *   l4p_track_bidir_merge  : traj [B][N][2][T], vis / dep [B][N][T] by the rule above; the reversed buffers are read mirrored (they are
+ *                            never flipped in memory).  mode 0: both passes; the outputs may be the forward buffers themselves.  mode 1: no
+ *                            forward pass (directions [-1]): forward-owned frames get the fill values 0 / -10 / 0, traj_f / vis_f / dep_f
+ *                            may be NULL. */
+int l4p_time_reverse(l4p_stream stream, const float* src, float* dst, int outer, int T, long long inner);
+int l4p_track_bidir_queries(l4p_stream stream, const float* q_bn3, int T, float* q_rev_bn3, int* need_count, int BN);
+int l4p_track_bidir_merge(l4p_stream stream, const float* q_bn3, const float* traj_f, const float* vis_f, const float* dep_f,
+                          const float* traj_r, const float* vis_r, const float* dep_r, float* traj, float* vis, float* dep, int B, int N,
+                          int T, int mode);
 
 /* ------------------------------------------------------------------------------------------------
  * Engine: holds the table of packed device weights and runs whole sub-networks with one call.

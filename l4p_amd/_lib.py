@@ -14,7 +14,7 @@ L4P_BF16 = 0
 L4P_F32 = 1
 L4P_F16 = 2  # IEEE half storage / f16 MFMA: the arithmetic class of the reference's "16-mixed" (fp16 autocast)
 
-ABI_VERSION = 20  # what l4p_abi_version() of the library this binding was written against returns (include/l4p_hip.h)
+ABI_VERSION = 21  # what l4p_abi_version() of the library this binding was written against returns (include/l4p_hip.h)
 
 EPI_DENSE, EPI_QKV, EPI_CONVT, EPI_MASKDOT = 0, 1, 2, 3
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
@@ -194,6 +194,9 @@ SIGNATURES = {
     "l4p_track_readout": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _I]),
     "l4p_track_prepare": (_I, [_VP, _VP, _VP, _I, _I, _VP, _VP, _VP, _VP, _I]),
     "l4p_track_commit": (_I, [_VP] * 9 + [_I] * 5 + [_VP] * 5 + [_I, _I]),
+    "l4p_time_reverse": (_I, [_VP, _VP, _VP, _I, _I, _LL]),
+    "l4p_track_bidir_queries": (_I, [_VP, _VP, _I, _VP, _VP, _I]),
+    "l4p_track_bidir_merge": (_I, [_VP] * 11 + [_I] * 4),
     "l4p_create": (_I, [_I, _I, C.POINTER(_VP)]),
     "l4p_destroy": (_I, [_VP]),
     "l4p_bind_weight": (_I, [_VP, C.c_char_p, _VP, _LL]),

@@ -226,6 +226,17 @@ class L4P_VideoMAE(torch.nn.Module):
         data = {k: (v.to(self.device) if torch.is_tensor(v) else v) for k, v in data.items()}
         if single:
             return self.forward_single_window(data, tasks)
+        trk = self.task_heads["track_2d"] if "track_2d" in tasks else None
+        dirs = sorted(getattr(trk, "estimation_directions", [1])) if trk is not None else [1]
+        if dirs == [1]:
+            return self._forward_windowed(data, tasks)
+        if dirs not in ([-1], [-1, 1]):
+            raise ValueError(f"estimation_directions {trk.estimation_directions}: expected [1], [-1], [1, -1] or [-1, 1]")
+        return self._forward_both_directions(data, tasks, trk, dirs)
+
+    def _forward_windowed(self, data: Dict[str, Any], tasks: List[str]) -> Dict[str, Any]:
+        """One causal pass over the windows of a clip (``data`` on the device)."""
+        T = data["rgb_b3thw"].shape[2]
         if self.window_batch > 1:
             from ..parallel import forward_windows_sharded  # the same code path the multi-GPU split uses, on one rank
 
@@ -235,6 +246,61 @@ class L4P_VideoMAE(torch.nn.Module):
         ws = self.window_size[0]
         feats2d = [self.video_encoder(data["rgb_b3thw"][:, :, int(s):int(s) + ws], tf, tT) for s in time_strides]
         return self.stitch_windows(feats2d, data, tasks, time_strides)
+
+    def _forward_both_directions(self, data: Dict[str, Any], tasks: List[str], trk, dirs: List[int]) -> Dict[str, Any]:
+        """estimation_directions [1, -1] / [-1] of the tracker, by the recipe of the reference's own assert (sparse_heads.py:242-245:
+        "Run twice, with and without video flipping, and then combine outputs"; DESIGN.md "Tracking in both time directions"):
+        the forward pass as it is, the tracker alone once more on the time-flipped clip with the queries ((float)T - tq, x, y), and
+        output frame g of a track from the forward pass iff ((float)g + 0.5f) - tq >= 0, else from the reversed pass at frame T-1-g.
+        It sits above the plain window loop and forward_windows_sharded alike, and decides from the full query set, so every rank of
+        a sharded call takes the same branch.
+
+        What the two passes share, and why the second cannot disturb the first: the forward pass's encoder feature blocks and tracker
+        outputs are tensors of their own, held by its result; the encoder workspace (Engine._ws) and the per-clip tracker workspaces
+        (Engine._trk_ws) ARE reused by the reversed pass - stitch_windows / forward_windows_sharded join every tracker and head stream
+        into the launching stream before they return, and the read-back of the count below then waits for that stream, so nothing of
+        the forward pass is in flight when the reversed pass starts."""
+        lib = _lib.load()
+        stream = lambda: torch.cuda.current_stream().cuda_stream  # noqa: E731
+        name = trk.task_name
+        keys = (f"{name}_traj_est_bn2t", f"{name}_vis_est_bn1t", f"{name}_depth_est_bn1t")
+        rgb = data["rgb_b3thw"]
+        B, _, T, H, W = rgb.shape
+        q = data["track_2d_pointquerries_bn3"].to(dtype=torch.float32).contiguous()
+        N = q.shape[1]
+        f32 = dict(dtype=torch.float32, device=self.device)
+        both = 1 in dirs
+        fwd_tasks = list(tasks) if both else [t for t in tasks if t != "track_2d"]
+        out: Dict[str, Any] = {}
+        if fwd_tasks:
+            with trk.select_direction(1):
+                out = self._forward_windowed(data, fwd_tasks)
+        need = 0
+        if N > 0:
+            q_rev = torch.empty_like(q)
+            count = torch.zeros(1, dtype=torch.int32, device=self.device)
+            _lib.check(lib.l4p_track_bidir_queries(stream(), q.data_ptr(), T, q_rev.data_ptr(), count.data_ptr(), B * N),
+                       "l4p_track_bidir_queries")
+            need = int(count.item())  # the one read-back: does any query have a frame before it?
+        if need == 0:
+            if not both:  # no forward tracker and no frame for the reversed one: the recursion's fill values
+                out[keys[0]] = torch.zeros(B, N, 2, T, **f32)
+                out[keys[1]] = torch.full((B, N, 1, T), -10.0, **f32)
+                out[keys[2]] = torch.zeros(B, N, 1, T, **f32)
+            return out
+        src = rgb.to(dtype=torch.float32).contiguous()
+        rgb_rev = torch.empty_like(src)
+        _lib.check(lib.l4p_time_reverse(stream(), src.data_ptr(), rgb_rev.data_ptr(), B * 3, T, H * W), "l4p_time_reverse")
+        with trk.select_direction(-1):
+            rev = self._forward_windowed({**data, "rgb_b3thw": rgb_rev, "track_2d_pointquerries_bn3": q_rev}, ["track_2d"])
+        fw = [out[k].contiguous() if both else None for k in keys]
+        rv = [rev[k].contiguous() for k in keys]
+        merged = [torch.empty_like(t) for t in rv]
+        _lib.check(lib.l4p_track_bidir_merge(stream(), q.data_ptr(), *[t.data_ptr() if t is not None else None for t in fw],
+                                             *[t.data_ptr() for t in rv], *[t.data_ptr() for t in merged], B, N, T, 0 if both else 1),
+                   "l4p_track_bidir_merge")
+        out.update(zip(keys, merged))
+        return out
 
     def time_strides(self, T: int) -> torch.Tensor:
         return torch.arange(0, T - self.window_size[0] + 1, self.window_stride_T)

@@ -9,6 +9,7 @@ sequences kernels over device buffers (no host synchronisation inside a window).
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import os
 from typing import Dict, List, Literal, Optional, Tuple
@@ -60,6 +61,7 @@ class VideoMAETrack2DSamHead(torch.nn.Module):
         self._rt = None
         self._engine_task = ""
         self.trace: Optional[list] = None  # set to [] to record per-window labels / queries (tests)
+        self._direction: Optional[int] = None  # the pass of a two-direction call that is running (select_direction)
 
     # ------------------------------------------------------------------------------------------------
     def _single_window_history_rows(self, N: int, P: int) -> int:
@@ -113,11 +115,13 @@ class VideoMAETrack2DSamHead(torch.nn.Module):
     def forward_windowed_core(self, enc_features_bpc_2dlist, track_2d_pointquerries_bn3: torch.Tensor,
                               track_2d_pointlabels_bn: torch.Tensor, time_strides: Optional[torch.Tensor] = None,
                               **kwargs) -> Dict[str, torch.Tensor]:
-        """Causal sliding-window tracking (sparse_heads.py:213-495), estimation_directions == [1]."""
+        """Causal sliding-window tracking (sparse_heads.py:213-495): ONE pass in the positive time direction.  With -1 among
+        estimation_directions the second pass is this same recursion on the time-flipped clip, and L4P_VideoMAE.forward is what
+        flips, runs and merges (the reference's recipe, sparse_heads.py:242-245); it says which pass this is through
+        ``select_direction``."""
         if self._rt is None:
             raise RuntimeError("tracker head has no weights: call load_state_dict on the model first")
-        assert len(self.estimation_directions) == 1 and self.estimation_directions[0] == 1, (
-            "Currently only positive direction estimation is supported for sliding window tracking.")
+        direction = self.pass_direction()
         if time_strides is None:  # if windowing is not needed just do a forward pass (sparse_heads.py:223-227)
             return self.forward(enc_features_bpc_2dlist[0], track_2d_pointquerries_bn3, track_2d_pointlabels_bn)
         lib = _lib.load()
@@ -176,6 +180,8 @@ class VideoMAETrack2DSamHead(torch.nn.Module):
                     # tracing does not change the schedule — the benchmarked stream configuration can be traced as it runs)
                     self.trace.append({"clip": b, "window": wi, "labels": labels.clone(), "queries": q_off.clone(),
                                        "prompt_labels": plabel.clone(), "valid_t": valid_t.clone()})
+                    if direction is not None:  # (a pass of a model that tracks in both directions: which one)
+                        self.trace[-1]["direction"] = direction
                 enc_last = enc_features_bpc_2dlist[wi].f32(-1)[b].contiguous()
                 # first window: the history of every track is the learned mask token (filled above) -> shared keys
                 # later windows: the second temporal half of every track's history is the mask token again (written by the
@@ -239,6 +245,30 @@ class VideoMAETrack2DSamHead(torch.nn.Module):
                 run_clip(b)
         return {f"{self.task_name}_traj_est_bn2t": traj_all, f"{self.task_name}_vis_est_bn1t": vis_all,
                 f"{self.task_name}_depth_est_bn1t": dep_all}
+
+    def pass_direction(self) -> Optional[int]:
+        """None with estimation_directions [1] (the one pass there is); else the direction of the pass L4P_VideoMAE.forward has
+        selected.  With -1 configured and no pass selected the head was called on its own: one causal pass would silently return one
+        direction where two were asked for, so it raises."""
+        dirs = sorted(self.estimation_directions)
+        if dirs == [1]:
+            return None
+        if dirs not in ([-1], [-1, 1]):
+            raise ValueError(f"estimation_directions {self.estimation_directions}: expected [1], [-1], [1, -1] or [-1, 1]")
+        if self._direction is None:
+            raise RuntimeError(
+                f"estimation_directions {self.estimation_directions}: the tracker head runs one causal pass; the reversed pass on the "
+                "time-flipped clip and the merge of the two are made by L4P_VideoMAE.forward - call that, not the head")
+        return self._direction
+
+    @contextlib.contextmanager
+    def select_direction(self, direction: int):
+        """L4P_VideoMAE.forward: the windowed passes run inside are the ``direction`` pass of a two-direction call."""
+        saved, self._direction = self._direction, int(direction)
+        try:
+            yield
+        finally:
+            self._direction = saved
 
     def join_streams(self) -> None:
         """Make the stream that launched the tracker wait for the clip streams (no-op when nothing is pending)."""

@@ -8,10 +8,12 @@ Each .npz holds one clip as a dataset's __getitem__ yields it: arrays under the 
 Prints one JSON line per clip (the scalars of that clip) and one with the mean of each metric over the clips that have a value.
 
   python tools/evaluate.py CLIPS_DIR --ckpt model.ckpt [--precision 16-mixed] [--depth-align median|none|lstsq|lstsq_inv]
-                           [--depth-log-errors] [--track-3d none|median|track_median|query]
+                           [--depth-log-errors] [--track-3d none|median|track_median|query] [--bidirectional]
 
 --depth-align lstsq_inv fits scale and shift in inverse depth; --depth-log-errors adds depth_sq_rel / rmse_log / log10 / silog;
 --track-3d MODE scores the (x, y, z) tracks in camera space (clips with track_2d_depth_bn1t and intrinsics_b44t) with the scale MODE.
+--bidirectional tracks every query in both time directions (estimation_directions [1, -1] on the tracker head and, with --raw, on the
+dataset, which then leaves track_2d_valid_bn1t as it is): the frames before a query are estimated and scored too.
   python tools/evaluate.py CLIPS_DIR --synthetic [--mini]      # seeded weights, as demo/demo.py --synthetic: plumbing, not numbers
 
 With --raw the .npz files hold RAW clips instead (the dataset's own resolution and length, rgb as float in [0, 1] or uint8): they
@@ -72,14 +74,14 @@ def mean_over_clips(rows) -> dict:
     return out
 
 
-def raw_loader(clips: str, resize, crop, spacing: float, seed: int):
+def raw_loader(clips: str, resize, crop, spacing: float, seed: int, directions=(1,)):
     """DataLoader(batch_size=1) over NpzClipDataset(clips): centre crop from the first frame; clips with their own queries keep
     them (scaled with the resize), the others get the uniform grid of ``spacing``."""
     from l4p_amd.data import NpzClipDataset
 
     torch.manual_seed(seed)
     ds = NpzClipDataset(clips, crop_size=tuple(crop) if crop else None, resize_size=tuple(resize) if resize else None, center_crop=True,
-                        start_crop_time=True, estimation_directions=[1], track_2d_querry_sampling_version="uniform",
+                        start_crop_time=True, estimation_directions=list(directions), track_2d_querry_sampling_version="uniform",
                         track_2d_querry_sampling_spacing=spacing, scale_queries_on_resize=True)
     return torch.utils.data.DataLoader(ds, batch_size=1, shuffle=False, num_workers=0)
 
@@ -105,6 +107,8 @@ def parse_args(argv=None):
     ap.add_argument("--depth-log-errors", action="store_true", help="also depth_sq_rel, depth_rmse_log, depth_log10, depth_silog")
     ap.add_argument("--track-3d", default=None, choices=["none", "median", "track_median", "query"], metavar="MODE",
                     help="score the 3D tracks with this scale: none, median (per clip), track_median, query (per track)")
+    ap.add_argument("--bidirectional", action="store_true",
+                    help="estimation_directions [1, -1]: track, and score, the frames before a query as well")
     ap.add_argument("--raw", action="store_true", help="the .npz files are raw clips: prepare them with NpzClipDataset on the GPU")
     ap.add_argument("--resize", type=int, nargs=2, default=None, metavar=("H", "W"), help="with --raw: resize_size")
     ap.add_argument("--crop", type=int, nargs=3, default=None, metavar=("T", "H", "W"), help="with --raw: crop_size (default: the "
@@ -142,12 +146,15 @@ def main():
     else:
         model = prepare_model(model_config_path=args.config, ckpt_path=args.ckpt, max_queries=args.max_queries,
                               precision=args.precision, accelerator="gpu")
+    directions = [1, -1] if args.bidirectional else [1]
+    if args.bidirectional:
+        model.l4p_model.task_heads["track_2d"].estimation_directions = directions
     model.metrics_module = L4PMetrics(depth_align=args.depth_align, track_3d=args.track_3d, depth_log_errors=args.depth_log_errors)
     rows = []
 
     def batches():
         if args.raw:
-            yield from raw_loader(args.clips, args.resize, args.crop, args.spacing, args.seed)
+            yield from raw_loader(args.clips, args.resize, args.crop, args.spacing, args.seed, directions)
             return
         for f in files:
             with np.load(f, allow_pickle=False) as z:
