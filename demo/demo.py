@@ -5,13 +5,17 @@ DataLoader(batch_size=1) -> prepare_model(...).forward(batch, tasks).  The outpu
 mask, track trails) rendered on the GPU; --recon4d DIR adds the camray task and writes the 4D reconstruction of the reference's 4D
 sections (generate_4D_visualization, demo.py:116-258) as PLY files under DIR; --view4d DIR adds the camray task too and renders what
 those sections end in (visualize_point_cloud_viser, demo.py:151-160: the point cloud of frame t, track trails and camera frustum from a
-free viewpoint) on the GPU, along an orbit camera path, as a video under DIR.
+free viewpoint) on the GPU, along an orbit camera path, as a video under DIR.  --scene-flow DIR (this project's own, no counterpart
+in the reference) adds the camray task as well and combines depth, flow and pose across time: per-pixel 3D motion in the world frame
+and the flow split into its camera-induced and its object part (l4p_amd.utils.scene_flow), as .npz, consistency numbers as .json and
+an [RGB | flow | camera-compensated flow] video; with --view4d the 4D video is rendered once more, coloured by 3D speed.
 
   python demo/demo.py --videos a.mp4 b.mp4 --ckpt weights/l4p_depth_flow_2d3dtrack_camray_dynseg_v1.ckpt   # needs mediapy
   python demo/demo.py --synthetic                      # no checkpoint / video files here: seeded weights + a seeded video
   python demo/demo.py --synthetic --vis out/           # + the five-panel result video (.mp4 with mediapy, PNG frames without)
   python demo/demo.py --synthetic --recon4d out/       # + 4D point clouds / track trails / frusta as PLY under out/
   python demo/demo.py --synthetic --view4d out/        # + the 4D result from a free viewpoint (.mp4 with mediapy, PNG frames without)
+  python demo/demo.py --synthetic --scene-flow out/    # + scene flow / camera-compensated flow (.npz, .json, video) under out/
   python demo/demo.py --davis DAVIS_ROOT --ckpt ...    # JPEGImages/480p/<seq>, Annotations/480p/<seq>: queries on the instance masks
   python demo/demo.py --dycheck DYCHECK_ROOT --ckpt ... --recon4d out/   # <seq>/dense/images, <seq>/calibration.txt
   python demo/demo.py --synthetic --davis X --vis out/ # a small seeded DAVIS (or --dycheck: DyCheck) tree in a temporary directory
@@ -63,6 +67,10 @@ def parse_args(argv=None):
     ap.add_argument("--view4d", default=None, metavar="DIR",
                     help="also run the camray task and render each video's 4D reconstruction from an orbiting viewpoint (points, track "
                          "trails, camera frusta; l4p_amd.utils.view4d.generate_4D_video) as <seq_name>_4d under DIR")
+    ap.add_argument("--scene-flow", default=None, metavar="DIR", dest="scene_flow",
+                    help="also run the camray task and write each video's dense scene flow, rigid and camera-compensated flow "
+                         "(<seq_name>_sceneflow.npz), their consistency numbers (.json) and an RGB | flow | compensated-flow video "
+                         "(l4p_amd.utils.scene_flow) under DIR; with --view4d also <seq_name>_4d_motion, the 4D video coloured by 3D speed")
     ap.add_argument("--bidirectional", action="store_true",
                     help="track every query in both time directions (estimation_directions [1, -1] on the tracker head and the dataset): "
                          "the frames before a query are estimated by a second tracker pass over the time-flipped clip")
@@ -85,8 +93,8 @@ def parse_args(argv=None):
 def plan(args):
     """(tasks, dataset keyword arguments) of the reference demo's section that ``args`` selects."""
     tasks = ["depth", "flow_2d_backward", "dyn_mask", "track_2d"]  # demo.py:82,99
-    if args.recon4d or args.view4d or args.dycheck:
-        tasks.append("camray")  # the reference's 4D sections (demo.py:116-258) add it
+    if args.recon4d or args.view4d or args.dycheck or args.scene_flow:
+        tasks.append("camray")  # the reference's 4D sections (demo.py:116-258) add it; scene flow needs the poses too
     kw = dict(crop_size=(args.frames, 224, 224), estimation_directions=[1, -1] if args.bidirectional else [1],
               track_2d_querry_sampling_spacing=args.spacing)
     if args.davis and (args.recon4d or args.view4d):
@@ -180,6 +188,8 @@ def run(args, model, dataset, tasks):
             recon_4d(batch, out, tasks, args.recon4d)
         if args.view4d:
             view_4d(batch, out, tasks, args.view4d)
+        if args.scene_flow:
+            scene_flow(batch, out, tasks, args.scene_flow, view4d_dir=args.view4d)
 
 
 def vis_2d(batch, out, tasks, out_dir):
@@ -225,9 +235,9 @@ def recon_4d(batch, out, tasks, out_dir):
           f"GPU reconstruction {(t1 - t0) * 1e3:.1f} ms, PLY writing {(t2 - t1) * 1e3:.0f} ms -> {path}")
 
 
-def view_4d(batch, out, tasks, out_dir):
+def view_4d(batch, out, tasks, out_dir, colors=None, suffix="_4d"):
     """generate_4D_video split into its GPU part (reconstruction, camera path, renderer), the copy to the host and the file writing,
-    each timed on its own."""
+    each timed on its own.  ``colors`` (uint8 [T H W, 3] on the device) replaces the reconstruction's point colours."""
     from l4p_amd.utils import recon4d, view4d, vis2d
 
     T, H, W = batch["rgb_b3thw"].shape[2:]
@@ -235,6 +245,8 @@ def view_4d(batch, out, tasks, out_dir):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     rec = recon4d.reconstruct_4d(batch, out, tasks)
+    if colors is not None:
+        rec["colors"] = colors
     path = view4d.orbit_views(rec, out["depth_est_b1thw"], T, T)
     K = out["traj3d_intrinsics_est_b16t"].reshape(4, 4, T)[:, :, 0].float().cpu().numpy().astype(np.float64)
     torch.cuda.synchronize()
@@ -245,11 +257,47 @@ def view_4d(batch, out, tasks, out_dir):
     t2 = time.perf_counter()
     frames = res["image"].cpu().numpy()
     t3 = time.perf_counter()
-    name = vis2d.write_video(frames, out_dir, batch["seq_name"][0] + "_4d")
+    name = vis2d.write_video(frames, out_dir, batch["seq_name"][0] + suffix)
     t4 = time.perf_counter()
     print(f"  4D view: {frames.shape[0]} views of {size[0]} x {size[1]}, look-at distance {path['d0']:.3g}; reconstruction + camera path "
           f"{(t1 - t0) * 1e3:.1f} ms, GPU render {(t2 - t1) * 1e3:.1f} ms, copy to host {(t3 - t2) * 1e3:.1f} ms, file writing "
           f"{(t4 - t3) * 1e3:.0f} ms -> {name}")
+
+
+def scene_flow(batch, out, tasks, out_dir, view4d_dir=None):
+    """Scene flow, rigid and camera-compensated flow of the clip (l4p_amd.utils.scene_flow): <seq>_sceneflow.npz (the four fields, the
+    scene flow as float16), <seq>_sceneflow.json (the consistency numbers; NaN where a class has no pixel) and the
+    [RGB | flow | camera-compensated flow] video <seq>_sceneflow.  With ``view4d_dir`` the 4D video is rendered a second time as
+    <seq>_4d_motion, its points coloured by 3D speed.  (With --synthetic the seeded weights give arbitrary poses and intrinsics: the
+    files are written, the numbers mean nothing.)"""
+    import json
+
+    from l4p_amd.utils import scene_flow as sf
+
+    seq = batch["seq_name"][0]
+    H, W = batch["rgb_b3thw"].shape[-2:]
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    res = sf.scene_flow_from_outputs(batch, out, tasks)
+    numbers = sf.consistency(res["summary_bt8"], pixels_per_frame=H * W)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    np.savez_compressed(os.path.join(out_dir, seq + "_sceneflow.npz"),
+                        scene_flow_backward_b3thw=res["scene_flow_backward_b3thw"].cpu().numpy().astype(np.float16),
+                        rigid_flow_2d_backward_b2thw=res["rigid_flow_2d_backward_b2thw"].cpu().numpy(),
+                        compensated_flow_2d_backward_b2thw=res["compensated_flow_2d_backward_b2thw"].cpu().numpy(),
+                        scene_flow_valid_b1thw=res["scene_flow_valid_b1thw"].cpu().numpy())
+    numbers = {k: float(v[0]) for k, v in numbers.items()}
+    with open(os.path.join(out_dir, seq + "_sceneflow.json"), "w") as fh:
+        json.dump(numbers, fh, indent=1)  # NaN is written as NaN (Python's json reads it back)
+    _, name = sf.generate_scene_flow_video(batch, out, tasks, out_dir, res=res)
+    t2 = time.perf_counter()
+    print(f"  scene flow: static rigid EPE {numbers['rigid_epe_static']:.3g} px, dynamic {numbers['rigid_epe_dynamic']:.3g} px, moving "
+          f"fraction {numbers['moving_fraction']:.3g}, valid fraction {numbers['valid_fraction']:.3g}; GPU {(t1 - t0) * 1e3:.1f} ms, "
+          f"files {(t2 - t1) * 1e3:.0f} ms -> {name}")
+    if view4d_dir:
+        view_4d(batch, out, tasks, view4d_dir, colors=sf.motion_colors(res)[0], suffix="_4d_motion")
 
 
 if __name__ == "__main__":

@@ -43,7 +43,8 @@ typedef void* l4p_stream; /* hipStream_t */
 typedef struct l4p_engine l4p_engine;
 
 const char* l4p_last_error(void);
-int l4p_abi_version(void); /* 21: tracking in both time directions (l4p_time_reverse, l4p_track_bidir_queries, l4p_track_bidir_merge);
+int l4p_abi_version(void); /* 22: dense scene flow and camera-compensated flow (l4p_scene_flow, l4p_scene_flow_summary, l4p_scene_flow_colors);
+                              * 21: tracking in both time directions (l4p_time_reverse, l4p_track_bidir_queries, l4p_track_bidir_merge);
                               * 20: the split-K rule of the 3x3x3 conv, stated once for caller and launcher (l4p_conv3d_splitk);
                               * 19: 3D-track metrics, inverse-depth alignment and log-space depth errors (l4p_metric_tracks3d,
                               * l4p_metric_tracks3d_ws_bytes, l4p_metric_depth_full, l4p_metric_depth_full_ws_bytes);
@@ -543,6 +544,40 @@ int l4p_view_mesh(l4p_stream stream, const float* frustum, int T, const float* c
 int l4p_view_resolve(l4p_stream stream, const unsigned long long* zbuf, const unsigned char* colors, const unsigned char* track_colors,
                      const long long* off, int T, int HW, long long n_track, const int* frame, int V, int Ho, int Wo, int bg_r,
                      int bg_g, int bg_b, unsigned char* image, float* depth, int* index);
+
+/* ------------------------------------------------------------------------------------------------
+ * Scene flow (csrc/sceneflow.hip; the definitions are this project's own, DESIGN.md "Scene flow"): the dense heads combined across
+ * time.  depth [B][1][T][H][W], flow [B][2][T][H][W] (backward: pixel p of frame t is found at p + flow in frame t - 1; channel 0 =
+ * x), P = world_T_cam and K = pixel intrinsics [B][16][T] (b44t; P affine, upper-left 3x3 of K), pixel (i = column, j = row) at
+ * integer coordinates.  For t >= 1, all in f32, every operation rounded on its own:
+ *   X  = P_t [D_t(p) K_t^-1 (i, j, 1); 1];   q = (i + flow_x, j + flow_y);   inside = 0 <= q_x <= W - 1 and 0 <= q_y <= H - 1
+ *   d' = w00 v00 + w01 v01 + w10 v10 + w11 v11 of D_{t-1} at rows y0 = floor(q_y), y1 = min(y0 + 1, H - 1) and columns x0, x1
+ *        likewise (v01 = D[y0][x1]), a = q - floor(q), w00 = (1 - a_y)(1 - a_x), w01 = (1 - a_y) a_x, w10 = a_y (1 - a_x), w11 = a_y a_x
+ *   X' = P_{t-1} [d' K_{t-1}^-1 (q_x, q_y, 1); 1];   scene = X' - X (world frame, pointing backward in time like the flow)
+ *   u  = P_{t-1}^-1 [X; 1];  if u_z > 1e-6: rigid = (K_{t-1} u)_xy / u_z - (i, j);   comp = flow - rigid
+ *   valid = inside and D_t(p) > 0 and d' > 0 and u_z > 1e-6 and every result finite; where valid is 0 the three fields are 0.
+ * K^-1 (general 3x3) and P^-1 (general affine) are formed in double and rounded to f32 once.  Frame 0 has no predecessor: fields
+ * and valid are 0 there, and nothing before frame 0 is read (T = 1: everything 0).  scene [B][3][T][H][W], rigid and comp
+ * [B][2][T][H][W], valid [B][1][T][H][W] uchar.  `mask` (the motion-mask logits, may be NULL) is accepted for symmetry with the
+ * summary and not read: the fields do not depend on it.  H W <= 2^30.
+ *
+ * Summary: rows [B][T][8] doubles = n_valid, n_static (valid and mask <= 0; all valid pixels when mask is NULL), n_dynamic (valid
+ * and mask > 0), sum |comp| over static, over dynamic, sum |scene| over static, over dynamic, n_moving (valid and |comp| > tau_px).
+ * Magnitudes are f32 (sqrtf of the unfused sum of squares, left to right, of the stored values) accumulated in double in a fixed
+ * order (per-block partials in ws, then a second pass; no atomics): the same bits on every run.
+ * ws: B T ceil(H W / L4P_SCENE_FLOW_CHUNK) 8 doubles.  B T < 65536.
+ *
+ * Colours: colors [B][T H W][3] uchar, frame-major as l4p_point_map's: a valid pixel takes lut[k] (lut [256][3] uchar) with
+ * k = floor(255 min(1, |scene| / s_max[0])) in f32, an invalid one (128, 128, 128).  s_max: one float on the device.
+ * Every entry returns L4P_E_INVALID, with nothing launched, for a size < 1 or a null pointer it needs.
+ * ---------------------------------------------------------------------------------------------- */
+#define L4P_SCENE_FLOW_CHUNK 1024
+int l4p_scene_flow(l4p_stream stream, const float* depth, const float* flow, const float* P, const float* K, const float* mask, int B,
+                   int T, int H, int W, float* scene, float* rigid, float* comp, unsigned char* valid);
+int l4p_scene_flow_summary(l4p_stream stream, const float* scene, const float* comp, const unsigned char* valid, const float* mask,
+                           int B, int T, int H, int W, float tau_px, double* ws, double* rows);
+int l4p_scene_flow_colors(l4p_stream stream, const float* scene, const unsigned char* valid, const unsigned char* lut, int B, int T,
+                          int H, int W, const float* s_max, unsigned char* colors);
 
 /* ------------------------------------------------------------------------------------------------
  * Evaluation metrics: what a metrics_module(batch, out, metadata) of L4PLitModule.step computes (l4p/l4p.py:74-78; the reference

@@ -14,7 +14,7 @@ L4P_BF16 = 0
 L4P_F32 = 1
 L4P_F16 = 2  # IEEE half storage / f16 MFMA: the arithmetic class of the reference's "16-mixed" (fp16 autocast)
 
-ABI_VERSION = 21  # what l4p_abi_version() of the library this binding was written against returns (include/l4p_hip.h)
+ABI_VERSION = 22  # what l4p_abi_version() of the library this binding was written against returns (include/l4p_hip.h)
 
 EPI_DENSE, EPI_QKV, EPI_CONVT, EPI_MASKDOT = 0, 1, 2, 3
 ACT_NONE, ACT_GELU, ACT_RELU = 0, 1, 2
@@ -151,6 +151,9 @@ SIGNATURES = {
     "l4p_view_splat": (_I, [_VP, _VP, _VP, _VP, _I, _I, _LL, _VP, _VP, _VP, _I, _I, _I, _F, _I, _F, _VP]),
     "l4p_view_mesh": (_I, [_VP, _VP, _I, _VP, _VP, _VP, _I, _I, _I, _I, _F, _VP]),
     "l4p_view_resolve": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _LL, _VP, _I, _I, _I, _I, _I, _I, _VP, _VP, _VP]),
+    "l4p_scene_flow": (_I, [_VP] * 6 + [_I] * 4 + [_VP] * 4),
+    "l4p_scene_flow_summary": (_I, [_VP] * 5 + [_I] * 4 + [_F, _VP, _VP]),
+    "l4p_scene_flow_colors": (_I, [_VP] * 4 + [_I] * 4 + [_VP, _VP]),
     "l4p_metric_ws_bytes": (_SZ, [_I, _LL, _I]),
     "l4p_metric_depth": (_I, [_VP, _VP, _VP, _VP, _I, _LL, _I, _F, _F, _VP, _SZ, _VP]),
     "l4p_metric_flow": (_I, [_VP, _VP, _VP, _VP, _I, _LL, _VP, _SZ, _VP]),
