@@ -27,11 +27,13 @@ from . import _lib
 from .ops import _p, _stream
 from .utils.recon4d import _f32
 
-DEPTH_ALIGN = {"none": 0, "median": 1, "lstsq": 2}  # L4P_DEPTH_ALIGN_* of l4p_metric_depth
-DEPTH_FULL_ALIGN = {**DEPTH_ALIGN, "lstsq_inv": 3}  # ... of l4p_metric_depth_full
-TRACK3D_SCALE = {"none": 0, "median": 1, "track_median": 2, "query": 3}  # L4P_TRACK3D_SCALE_*
-DENSE_OUT, TRACKS_OUT, TRACKS_COUNTS, CAMERAS_OUT = 16, 32, 18, 8  # L4P_METRIC_*_OUT / _COUNTS
-DEPTH_FULL_OUT = 24  # L4P_METRIC_DEPTH_FULL_OUT
+DEPTH_ALIGN = {"none": _lib.L4P_DEPTH_ALIGN_NONE, "median": _lib.L4P_DEPTH_ALIGN_MEDIAN,
+               "lstsq": _lib.L4P_DEPTH_ALIGN_LSTSQ}  # the modes of l4p_metric_depth
+DEPTH_FULL_ALIGN = {**DEPTH_ALIGN, "lstsq_inv": _lib.L4P_DEPTH_ALIGN_LSTSQ_INV}  # ... of l4p_metric_depth_full
+TRACK3D_SCALE = {"none": _lib.L4P_TRACK3D_SCALE_NONE, "median": _lib.L4P_TRACK3D_SCALE_MEDIAN,
+                 "track_median": _lib.L4P_TRACK3D_SCALE_TRACK_MEDIAN, "query": _lib.L4P_TRACK3D_SCALE_QUERY}
+DENSE_OUT, TRACKS_OUT, CAMERAS_OUT = _lib.L4P_METRIC_DENSE_OUT, _lib.L4P_METRIC_TRACKS_OUT, _lib.L4P_METRIC_CAMERAS_OUT
+TRACKS_COUNTS, DEPTH_FULL_OUT = _lib.L4P_METRIC_TRACKS_COUNTS, _lib.L4P_METRIC_DEPTH_FULL_OUT
 TAP_THRESHOLDS = (1, 2, 4, 8, 16)
 TASKS = ("depth", "flow", "dyn_mask", "track_2d", "camray")
 

@@ -32,9 +32,9 @@ def _mode(pre_post_fn: Optional[str]) -> int:
     raise ValueError(f"Unknown pre_post_fn: {pre_post_fn}")
 
 
-AFFINE_SCRATCH_DOUBLES = 4096  # L4P_AFFINE_SCRATCH_DOUBLES (include/l4p_hip.h)
-ALIGN_INVERSE, ALIGN_RATIO_MEAN = 1, 2
-QUANTILE_WS_UINTS = 2052  # L4P_QUANTILE_WS_UINTS
+AFFINE_SCRATCH_DOUBLES = _lib.L4P_AFFINE_SCRATCH_DOUBLES
+ALIGN_INVERSE, ALIGN_RATIO_MEAN = _lib.L4P_ALIGN_INVERSE, _lib.L4P_ALIGN_RATIO_MEAN
+QUANTILE_WS_UINTS = _lib.L4P_QUANTILE_WS_UINTS
 
 
 class LstSqAffineAligner(WindowOverlapAligner):

@@ -170,7 +170,7 @@ def reconstruct_4d(batch: dict, out: dict, tasks: List[str]) -> Dict[str, torch.
                    "l4p_recon_track_prep")
         off_h = off.cpu()  # the one host read-back: output sizes and the median's rank
         total, nvis = int(off_h[T]), int(off_h[T + 1])
-        ws = torch.empty(2052, dtype=torch.int32, device=dev)  # L4P_QUANTILE_WS_UINTS
+        ws = torch.empty(_lib.L4P_QUANTILE_WS_UINTS, dtype=torch.int32, device=dev)
         sel = torch.empty(1, dtype=torch.float32, device=dev)
         _lib.check(lib.l4p_recon_track_scale(st, _p(ratios), N * T, nvis, _p(flag), _p(ws), _p(sel), _p(scale)),
                    "l4p_recon_track_scale")

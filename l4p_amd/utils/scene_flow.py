@@ -25,7 +25,7 @@ from . import recon4d, vis2d
 
 SUMMARY_COLUMNS = ("n_valid", "n_static", "n_dynamic", "sum_comp_static", "sum_comp_dynamic", "sum_scene_static", "sum_scene_dynamic",
                    "n_moving")
-SUMMARY_CHUNK = 1024  # L4P_SCENE_FLOW_CHUNK (include/l4p_hip.h)
+SUMMARY_CHUNK = _lib.L4P_SCENE_FLOW_CHUNK
 INVALID_COLOUR = (128, 128, 128)
 
 
@@ -152,7 +152,7 @@ def default_s_max(res: Dict[str, torch.Tensor]) -> torch.Tensor:
     scene = res["scene_flow_backward_b3thw"]
     assert scene.is_cuda, "default_s_max runs on the GPU"
     mag = (scene * scene).sum(dim=1).sqrt().contiguous()
-    ws = torch.empty(2052, dtype=torch.int32, device=scene.device)  # L4P_QUANTILE_WS_UINTS
+    ws = torch.empty(_lib.L4P_QUANTILE_WS_UINTS, dtype=torch.int32, device=scene.device)
     q = torch.empty(1, dtype=torch.float32, device=scene.device)
     _lib.check(_lib.load().l4p_quantile(_stream(), _p(mag), mag.numel(), 0.98, _p(ws), _p(q)), "l4p_quantile")
     return torch.where(q == 0, torch.ones_like(q), q)

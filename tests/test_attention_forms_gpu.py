@@ -30,7 +30,7 @@ from l4p_amd._lib import L4P_BF16, L4P_F16, L4P_F32
 from tests.test_gemm8p_gpu import prof_tags
 from tests.test_kernels_gpu import LOG2E, _attn_inputs, as_mode, check_attn
 
-E_INVALID = -1  # L4P_E_INVALID
+E_INVALID = _lib.L4P_E_INVALID
 MODES16 = pytest.mark.parametrize("mode", [L4P_BF16, L4P_F16], ids=["bf16", "f16"])
 
 

@@ -140,7 +140,7 @@ def test_dpt_workspace_too_small_is_refused_and_its_size_ignores_the_fold_knob(d
         out = torch.zeros((B, out_ch) + tuple(osz), dtype=torch.float32, device="cuda")
         args = (eng.handle, torch.cuda.current_stream().cuda_stream, task.encode(), C.byref(dc), hp, B, ws.data_ptr())
         rc = lib.l4p_dpt_forward(*args, need // 2, out.data_ptr())
-        assert rc == -1 and "workspace too small" in lib.l4p_last_error().decode(), (rc, lib.l4p_last_error())  # L4P_E_INVALID
+        assert rc == _lib.L4P_E_INVALID and "workspace too small" in lib.l4p_last_error().decode(), (rc, lib.l4p_last_error())
         _lib.check(lib.l4p_dpt_forward(*args, need, out.data_ptr()), "l4p_dpt_forward")
         torch.cuda.synchronize()
         assert torch.equal(out, want), task

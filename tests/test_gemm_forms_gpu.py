@@ -31,7 +31,7 @@ from tests.gemm_forms_cases import case_id
 from tests.test_gemm8p_gpu import prof_tags
 from tests.test_kernels_gpu import check
 
-E_INVALID = -1  # L4P_E_INVALID
+E_INVALID = _lib.L4P_E_INVALID
 PAD, GUARD_ROWS = G.PAD, 16
 SENTINEL = -24576.0  # (exact in bf16 and f16; the data are of order 1 to 10)
 CLASSES = ("gemm", "gemm_small", "conv3d")

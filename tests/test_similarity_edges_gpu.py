@@ -286,7 +286,7 @@ def test_ransac_repeated_sample_points_still_give_a_rotation(dev):
 def test_ransac_refusals_leave_out_untouched(dev):
     src, dst, _ = ransac_case(257, 51, 1.7, 0.3, 78)
     for n, trials, min_samples in [(2, 100, 3), (9, 100, 10), (257, 100, 2), (257, 100, 33), (257, 0, 3), (257, -1, 3)]:
-        got = run_ransac(src[:n], dst[:n], Q98, trials, min_samples, 1, expect_rc=-1)  # L4P_E_INVALID
+        got = run_ransac(src[:n], dst[:n], Q98, trials, min_samples, 1, expect_rc=_lib.L4P_E_INVALID)
         assert (got == SENTINEL).all(), (n, trials, min_samples, got)
         assert "similarity_ransac" in _lib.load().l4p_last_error().decode()
 

@@ -25,7 +25,7 @@ from l4p_amd._lib import ACT_GELU, ACT_NONE, L4P_F32
 from tests import kernel_refs as R
 from tests.test_kernels_gpu import MODES, as_mode, check, rnd
 
-E_INVALID = -1  # L4P_E_INVALID
+E_INVALID = _lib.L4P_E_INVALID
 SENT = 0xA5     # sentinel byte of pre-filled buffers
 
 

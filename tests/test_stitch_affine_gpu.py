@@ -179,7 +179,7 @@ def test_quantile_and_rank_select_on_signed_values(dev):
 
     lib = _lib.load()
     st = torch.cuda.current_stream().cuda_stream
-    ws = torch.empty(2052, dtype=torch.int32, device="cuda")
+    ws = torch.empty(_lib.L4P_QUANTILE_WS_UINTS, dtype=torch.int32, device="cuda")
     out = torch.empty(1, dtype=torch.float32, device="cuda")
     g = torch.Generator().manual_seed(3)
     x = torch.randn(10007, generator=g)

@@ -10,7 +10,7 @@ from l4p_amd import _lib
 from l4p_amd.ops import _p, _stream
 from tests import track_bidir_restate as rs
 
-INVALID = -1  # L4P_E_INVALID
+INVALID = _lib.L4P_E_INVALID
 
 
 def _bits(a):

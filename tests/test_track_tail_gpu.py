@@ -30,7 +30,7 @@ from l4p_amd import _lib
 from tests import kernel_refs as R
 from tests.test_kernels_gpu import rnd
 
-E_INVALID = -1       # L4P_E_INVALID
+E_INVALID = _lib.L4P_E_INVALID
 SENT = 0xA5          # sentinel byte of pre-filled buffers
 SENT32 = -1515870811  # 0xA5A5A5A5 as int32
 GUARD = 64           # sentinel floats around and between the outputs
