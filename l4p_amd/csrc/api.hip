@@ -80,7 +80,9 @@ int l4p_conv3d_subpixel(l4p_stream stream, int dtype, const l4p_gemm_desc* d) {
 }
 int l4p_layernorm(l4p_stream stream, int dtype, const float* x, const float* gamma, const float* beta, float eps,
                   void* out_T, float* out_f32, int M, int C) {
-    return launch_layernorm(dtype, x, gamma, beta, eps, out_T, out_f32, M, C, (hipStream_t)stream);
+    LnParams p = ln_params(LN_ROWS, x, gamma, beta, eps, M, C);
+    p.out_T = out_T, p.out_f32 = out_f32;
+    return launch_layernorm(dtype, p, (hipStream_t)stream);
 }
 int l4p_attention(l4p_stream stream, int dtype, const void* q, const void* kt, const void* vt, void* out, int B, int S,
                   int H, int Dh, float scale) {
@@ -258,9 +260,9 @@ int l4p_encoder_forward(l4p_engine* e, l4p_stream stream_, const float* rgb, int
             if (layer == c.depth) {
                 // features_list[-1] = norm(x)  (l4p_videomae.py:115)
                 const float *ng = g.Wf("norm.g"), *nb = g.Wf("norm.b");
-                g.launch([&] {
-                    return launch_layernorm(dt, w.x, ng, nb, c.ln_eps, tap_T ? tap_T[i] : nullptr, tap_f32 ? tap_f32[i] : nullptr, M, C, stream);
-                });
+                LnParams p = ln_params(LN_ROWS, w.x, ng, nb, c.ln_eps, M, C);
+                p.out_T = tap_T ? tap_T[i] : nullptr, p.out_f32 = tap_f32 ? tap_f32[i] : nullptr;
+                g.launch([&] { return launch_layernorm(dt, p, stream); });
             } else {
                 if (tap_f32 && tap_f32[i])
                     g.launch([&] {
@@ -300,6 +302,16 @@ int l4p_encoder_forward(l4p_engine* e, l4p_stream stream_, const float* rgb, int
     bool pending = false;
     int pending_sk = 0;
     const float* pending_bias = nullptr;
+    // xn = norm(x), or - add: what the projection before it left instead of summing it into x - x += add, xn = norm(x) in one pass
+    enum { ADD_NOTHING, ADD_DELTA, ADD_PARTIALS };
+    auto norm = [&](const float* ng, const float* nb, int add, int nsplit = 0, const float* bias = nullptr) {
+        LnParams p = ln_params(add == ADD_NOTHING ? LN_ROWS : LN_RES, w.x, ng, nb, c.ln_eps, M, C);
+        p.out_T = w.xn;
+        if (add != ADD_NOTHING) p.out_sum = w.x;
+        if (add == ADD_DELTA) p.delta_T = delta;
+        if (add == ADD_PARTIALS) p.part = w.sk, p.nsplit = nsplit, p.pbias = bias;
+        g.launch([&] { return launch_layernorm(dt, p, stream); });
+    };
     for (int l = 0; l < last && l < c.depth && !g.rc; ++l) {
         char key[48];
         auto Wb = [&](const char* name) {
@@ -313,19 +325,13 @@ int l4p_encoder_forward(l4p_engine* e, l4p_stream stream_, const float* rgb, int
         const float *qkvb = Wbf("qkv.b"), *projb = Wbf("proj.b"), *fc1b = Wbf("fc1.b"), *fc2b = Wbf("fc2.b");
         // x = x + proj(attn(norm1(x)))            modeling_finetune.py:247, :169-190
         if (pending) {  // x += the previous block's MLP output (left in the engine dtype), then norm1: one pass over x
-            g.launch([&] {
-                return launch_layernorm_res(dt, w.x, 0, delta, ln1g, ln1b, c.ln_eps, w.xn, nullptr, M, C, nullptr, 0, nullptr, nullptr, 1, 0,
-                                            stream, w.x);
-            });
+            norm(ln1g, ln1b, ADD_DELTA);
             pending = false;
         } else if (pending_sk > 0) {  // ... left as split-K partials: bias + slices summed here instead of in a finish pass
-            g.launch([&] {
-                return launch_layernorm_res(dt, w.x, 0, nullptr, ln1g, ln1b, c.ln_eps, w.xn, nullptr, M, C, nullptr, 0, nullptr, nullptr, 1, 0,
-                                            stream, w.x, w.sk, pending_sk, pending_bias);
-            });
+            norm(ln1g, ln1b, ADD_PARTIALS, pending_sk, pending_bias);
             pending_sk = 0;
         } else {
-            g.launch([&] { return launch_layernorm(dt, w.x, ln1g, ln1b, c.ln_eps, w.xn, nullptr, M, C, stream); });
+            norm(ln1g, ln1b, ADD_NOTHING);
         }
         GemmParams p = dense(w.xn, M, C, C, qkvw, C, 3 * H * Dp);
         p.bias = qkvb;
@@ -346,13 +352,7 @@ int l4p_encoder_forward(l4p_engine* e, l4p_stream stream_, const float* rgb, int
             p.res1 = w.x, p.res_f32 = 1, p.ldr = C, p.out_f32 = w.x;
         g.gemm(0, p);
         // x = x + fc2(gelu(fc1(norm2(x))))         modeling_finetune.py:248, :62-69
-        if (defer)
-            g.launch([&] {
-                return launch_layernorm_res(dt, w.x, 0, delta, ln2g, ln2b, c.ln_eps, w.xn, nullptr, M, C, nullptr, 0, nullptr, nullptr, 1, 0,
-                                            stream, w.x);
-            });
-        else
-            g.launch([&] { return launch_layernorm(dt, w.x, ln2g, ln2b, c.ln_eps, w.xn, nullptr, M, C, stream); });
+        norm(ln2g, ln2b, defer ? ADD_DELTA : ADD_NOTHING);
         p = dense(w.xn, M, C, C, fc1w, C, c.mlp_hidden);
         p.bias = fc1b;
         p.act = ACT_GELU;

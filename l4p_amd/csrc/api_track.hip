@@ -6,22 +6,30 @@ extern "C" {
 int l4p_layernorm_res(l4p_stream s, int dtype, const float* x, int x_mod, const void* delta_T, const float* gamma, const float* beta,
                       float eps, void* out_T, float* out_f32, int M, int C, const float* add, int add_mod, void* out_T2,
                       const float* x_shared, int x_period, int x_split, float* out_stats) {
-    return launch_layernorm_res(dtype, x, x_mod, delta_T, gamma, beta, eps, out_T, out_f32, M, C, add, add_mod, out_T2, x_shared, x_period,
-                                x_split, (hipStream_t)s, nullptr, nullptr, 0, nullptr, out_stats);
+    LnParams p = ln_params(LN_RES, x, gamma, beta, eps, M, C);
+    p.x_mod = x_mod, p.delta_T = delta_T, p.x_shared = x_shared, p.x_period = x_period, p.x_split = x_split;
+    p.add = add, p.add_mod = add_mod, p.out_T = out_T, p.out_f32 = out_f32, p.out_T2 = out_T2, p.out_stats = out_stats;
+    return launch_layernorm(dtype, p, (hipStream_t)s);
 }
 int l4p_layernorm_chain(l4p_stream s, int dtype, const float* x_shared_rows, int x_mod, const void* delta_prev_T, const float* stats_prev,
                         const float* gamma_prev, const float* beta_prev, const void* delta_T, const float* gamma, const float* beta, float eps,
                         void* out_T, float* out_f32, int M, int C, const float* add, int add_mod, void* out_T2) {
-    return launch_layernorm_chain(dtype, x_shared_rows, x_mod, delta_prev_T, stats_prev, gamma_prev, beta_prev, delta_T, gamma, beta, eps, out_T,
-                                  out_f32, M, C, add, add_mod, out_T2, (hipStream_t)s);
+    LnParams p = ln_params(LN_CHAIN, x_shared_rows, gamma, beta, eps, M, C);
+    p.x_mod = x_mod, p.dprev_T = delta_prev_T, p.stats_in = stats_prev, p.g0 = gamma_prev, p.b0 = beta_prev, p.delta_T = delta_T;
+    p.add = add, p.add_mod = add_mod, p.out_T = out_T, p.out_f32 = out_f32, p.out_T2 = out_T2;
+    return launch_layernorm(dtype, p, (hipStream_t)s);
 }
 int l4p_layernorm_ex(l4p_stream s, int dtype, const float* x, const float* gamma, const float* beta, float eps,
                      void* out_T, float* out_f32, int M, int C, const float* add, int add_mod, void* out_T2, int act) {
-    return launch_layernorm_ex(dtype, x, gamma, beta, eps, out_T, out_f32, M, C, add, add_mod, out_T2, act, (hipStream_t)s);
+    LnParams p = ln_params(LN_ROWS, x, gamma, beta, eps, M, C);
+    p.act = act, p.add = add, p.add_mod = add_mod, p.out_T = out_T, p.out_f32 = out_f32, p.out_T2 = out_T2;
+    return launch_layernorm(dtype, p, (hipStream_t)s);
 }
 int l4p_layernorm_t(l4p_stream s, int dtype, const void* x_T, const float* gamma, const float* beta, float eps, void* out_T,
                     int M, int C, int act) {
-    return launch_layernorm_T(dtype, x_T, gamma, beta, eps, out_T, M, C, act, (hipStream_t)s);
+    LnParams p = ln_params(LN_ROWS, x_T, gamma, beta, eps, M, C);
+    p.x_is_T = 1, p.act = act, p.out_T = out_T;
+    return launch_layernorm(dtype, p, (hipStream_t)s);
 }
 int l4p_track_tokens(l4p_stream s, const float* queries, const float* labels, const float* pfeat, const float* plabel,
                      const float* gauss, const float* mask_tokens, const float* point_emb0, const float* point_emb1,

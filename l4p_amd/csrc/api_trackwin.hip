@@ -50,7 +50,9 @@ struct TW : Graph {
     void ln(const float* x32, const std::string& key, float eps, void* oT, float* o32, long long M, int Cc, const float* add,
             int add_mod, void* oT2, int act) {
         const float *g = Wf(key + ".g"), *b = Wf(key + ".b");
-        launch([&] { return launch_layernorm_ex(dt, x32, g, b, eps, oT, o32, (int)M, Cc, add, add_mod, oT2, act, st); });
+        LnParams p = ln_params(LN_ROWS, x32, g, b, eps, (int)M, Cc);
+        p.act = act, p.add = add, p.add_mod = add_mod, p.out_T = oT, p.out_f32 = o32, p.out_T2 = oT2;
+        launch([&] { return launch_layernorm(dt, p, st); });
     }
     void attn(int kind, const void* q, const void* k, const void* v, void* out, int N, int P, int D, int heads) {
         launch([&] { return launch_small_attn(dt, kind, q, k, v, out, N, P, D, heads, st); });
@@ -324,19 +326,17 @@ int run(TW& c, const l4p_track_cfg& g, const float* enc_last, float* hist, const
             // (after the last layer nothing adds to the float keys any more: only the T copies are written)
             float* o32 = l + 1 < g.sam_depth && !chain_next ? k32 : nullptr;
             const float *n4g = c.Wf(lo + "norm4.g"), *n4b = c.Wf(lo + "norm4.b");
+            LnParams p = ln_params(chained ? LN_CHAIN : LN_RES, chained ? ks32 : cur32, n4g, n4b, 1e-5f, (int)NP, Cc);
+            p.delta_T = delta, p.add = pos, p.add_mod = P, p.out_T = kT, p.out_T2 = kP;
             if (chained) {  // (the previous layer left its update in k32's storage and its statistics in chain_stats)
-                const float *pg = c.Wf(chain_norm + ".g"), *pb = c.Wf(chain_norm + ".b");
-                c.launch([&] {
-                    return launch_layernorm_chain(c.dt, ks32, P, k32, chain_stats, pg, pb, delta, n4g, n4b, 1e-5f, kT,
-                                                  l + 1 < g.sam_depth ? kc32 : nullptr, (int)NP, Cc, pos, P, kP, c.st);
-                });
+                p.x_mod = P, p.dprev_T = k32, p.stats_in = chain_stats;
+                p.g0 = c.Wf(chain_norm + ".g"), p.b0 = c.Wf(chain_norm + ".b");
+                p.out_f32 = l + 1 < g.sam_depth ? kc32 : nullptr;
             } else {
-                c.launch([&] {
-                    return launch_layernorm_res(c.dt, cur32, shared ? P : 0, delta, n4g, n4b, 1e-5f, kT, o32, (int)NP, Cc, pos, P, kP,
-                                                half_shared && l == 0 ? kh32 : nullptr, P, P / 2, c.st, nullptr, nullptr, 0, nullptr,
-                                                chain_next ? chain_stats : nullptr);
-                });
+                p.x_mod = shared ? P : 0, p.out_f32 = o32, p.out_stats = chain_next ? chain_stats : nullptr;
+                if (half_shared && l == 0) p.x_shared = kh32, p.x_period = P, p.x_split = P / 2;
             }
+            c.launch([&] { return launch_layernorm(c.dt, p, c.st); });
             if (chained) cur32_after_chain = kc32;
             chained = chain_next;
             chain_norm = lo + "norm4";
@@ -423,8 +423,9 @@ int run(TW& c, const l4p_track_cfg& g, const float* enc_last, float* hist, const
         p.epi = EPI_CONVT;
         p.kt = p.kh = p.kw = 2, p.Cout = d0;
         c.gemm(0, p);
-        const float *lg = c.Wf("up_ln.g"), *lb = c.Wf("up_ln.b");
-        c.launch([&] { return launch_layernorm_T(c.dt, u0T, lg, lb, 1e-6f, u0T, (int)M1, d0, ACT_GELU, c.st); });
+        LnParams ln = ln_params(LN_ROWS, u0T, c.Wf("up_ln.g"), c.Wf("up_ln.b"), 1e-6f, (int)M1, d0);
+        ln.x_is_T = 1, ln.act = ACT_GELU, ln.out_T = u0T;  // (in place)
+        c.launch([&] { return launch_layernorm(c.dt, ln, c.st); });
     }
     // up1 (ConvTranspose (1,2,2) + GELU) fused with the hyper-network mask product (mask_decoder.py:136-139)
     const int Tl = nt * 2, hl = nh * 4, wl = nw * 4;

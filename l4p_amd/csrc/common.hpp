@@ -86,6 +86,89 @@ template <> __device__ __forceinline__ bf16_t from_f32<bf16_t>(float v) { return
 template <> __device__ __forceinline__ f16_t from_f32<f16_t>(float v) { return (f16_t)v; }
 template <typename T> __device__ __forceinline__ float to_f32(T v) { return (float)v; }
 
+template <typename T> struct Vec8;  // 8 consecutive elements of T as floats
+template <> struct Vec8<bf16_t> {
+    static __device__ __forceinline__ void load(const bf16_t* p, float* v) {
+        const bf16x8 t = *(const bf16x8*)p;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = (float)t[k];
+    }
+    static __device__ __forceinline__ void store(bf16_t* p, const float* v) {
+        bf16x8 t;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) t[k] = (bf16_t)v[k];
+        *(bf16x8*)p = t;
+    }
+};
+template <> struct Vec8<f16_t> {
+    static __device__ __forceinline__ void load(const f16_t* p, float* v) {
+        const f16x8 t = *(const f16x8*)p;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) v[k] = (float)t[k];
+    }
+    static __device__ __forceinline__ void store(f16_t* p, const float* v) {
+        f16x8 t;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) t[k] = (f16_t)v[k];
+        *(f16x8*)p = t;
+    }
+};
+template <> struct Vec8<float> {
+    static __device__ __forceinline__ void load(const float* p, float* v) {
+        const f32x4 a = *(const f32x4*)p, b = *(const f32x4*)(p + 4);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            v[k] = a[k];
+            v[4 + k] = b[k];
+        }
+    }
+    static __device__ __forceinline__ void store(float* p, const float* v) {
+        *(f32x4*)p = (f32x4){v[0], v[1], v[2], v[3]};
+        *(f32x4*)(p + 4) = (f32x4){v[4], v[5], v[6], v[7]};
+    }
+};
+
+// 4 consecutive elements (head dims only need % 4 == 0).  raw_t: the four as loaded, for operands that wait in registers (a 16-bit
+// quad is two registers, converted where it is used)
+template <typename T> struct Vec4;
+template <> struct Vec4<bf16_t> {
+    typedef bf16x4 raw_t;
+    static __device__ __forceinline__ void load(const bf16_t* p, float* v) {
+        const bf16x4 t = *(const bf16x4*)p;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = (float)t[k];
+    }
+    static __device__ __forceinline__ void store(bf16_t* p, const float* v) {
+        bf16x4 t;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) t[k] = (bf16_t)v[k];
+        *(bf16x4*)p = t;
+    }
+};
+template <> struct Vec4<f16_t> {
+    typedef f16x4 raw_t;
+    static __device__ __forceinline__ void load(const f16_t* p, float* v) {
+        const f16x4 t = *(const f16x4*)p;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = (float)t[k];
+    }
+    static __device__ __forceinline__ void store(f16_t* p, const float* v) {
+        f16x4 t;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) t[k] = (f16_t)v[k];
+        *(f16x4*)p = t;
+    }
+};
+template <> struct Vec4<float> {
+    typedef f32x4 raw_t;
+    static __device__ __forceinline__ void load(const float* p, float* v) {
+        const f32x4 a = *(const f32x4*)p;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) v[k] = a[k];
+    }
+    static __device__ __forceinline__ void store(float* p, const float* v) { *(f32x4*)p = (f32x4){v[0], v[1], v[2], v[3]}; }
+};
+
 // exact (erf) GELU, matches torch.nn.GELU() default
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 // The same GELU for the bf16 engine, branch free and ~3x fewer VALU slots than erff (which runs both of its divergent

@@ -10,116 +10,143 @@
 // LayerNorm over the last dim of a float [M][C] residual stream (reference: nn.LayerNorm eps=1e-6
 // in the encoder, l4p_videomae.py:177; eps=1e-5 in the SAM two-way transformer, transformer.py:145-153;
 // LayerNorm3d over channels, mask_decoder.py:145-157 == the same row LN in channels-last layout).
-// Two-pass in registers (mean, then centred variance) like ATen.  out_T and/or out_f32 may be given.
+// Two-pass in registers (mean, then centred variance) like ATen.  ln_select.hpp: the parameters of a launch (LnParams) and which of
+// the kernels below it gets; launch_layernorm at the end of this section starts it.
 // ---------------------------------------------------------------------------------------------
-// XT: the input row is stored as T (the bf16 engine's activations) instead of float - half the bytes in; it may alias
-// out_T (a wave holds its rows in registers before it stores anything).
-// ROWS: rows per wave (all requested before the first is reduced).  Measured on the 1M x 352 LayerNorm + GELU of the tracker:
-// 1 row 556 us, 2 rows 696 us, 4 rows 889 us - that launch is VALU-bound (GELU on 369 M elements), not latency-bound, and
-// more rows only add register pressure; every launcher uses ROWS = 1.
-// RES: the row normalised is x[row % x_mod] + delta[row] (delta in the engine dtype): the tracker's "keys += attention
-// output; keys = LayerNorm(keys)" (sam/transformer.py:183-185) with the sum formed HERE instead of in the projection's
-// epilogue - the float key stream is read once by this kernel instead of read + written by the GEMM and read again.
-#ifdef LN_NT  // (probe: streaming hints on the LayerNorm's row loads / stores.  Measured, same call: the tracker's 369 MB-per-stream
-              //  key LayerNorms 470 -> 449 us / 581 -> 582 us, the encoder's 8192-row ones 29.3 -> 31.9 us - their output is the
-              //  next GEMM's operand and wants to stay in cache; c3 +-0.4 %: not adopted)
-#define LN_ST(ptr, val) __builtin_nontemporal_store((val), (ptr))
-#define LN_LD(ptr) __builtin_nontemporal_load(ptr)
-#else
-#define LN_ST(ptr, val) (*(ptr) = (val))
-#define LN_LD(ptr) (*(ptr))
-#endif
+// ---- what the forms share: the affine, a typed quad, the wave's row statistics, the tail ----
 // y = (v - mean) * rstd * g + b, written ONCE: the chained key LayerNorm below re-derives another launch's float result from its
 // inputs and stored statistics, bit for bit - both must round the same way whatever the compiler would contract in each context
 __device__ __forceinline__ float ln_affine(float v, float mean, float rstd, float g, float b) {
     return __builtin_fmaf((v - mean) * rstd, g, b);
 }
-template <typename T, int MAXV, bool XT = false, int ROWS = 1, bool RES = false, bool PART = false>
+// where quad idx of a row of T lies (indexed as a quad, so that idx folds into the memory instruction's offset)
+template <typename T>
+__device__ __forceinline__ T* ln_quad_at(T* row, int idx) {
+    return (T*)((typename Vec4<std::remove_const_t<T>>::raw_t*)row + idx);
+}
+// quad idx of a row stored as T, as floats; zero when it lies outside the row (branch-free: the load is clamped, not predicated, so
+// all slots of a lane are requested at once)
+template <typename T>
+__device__ __forceinline__ f32x4 ln_quad(const T* row, int idx, bool in) {
+    float t[4];
+    Vec4<T>::load(ln_quad_at(row, in ? idx : 0), t);
+    return (f32x4){in ? t[0] : 0.f, in ? t[1] : 0.f, in ? t[2] : 0.f, in ? t[3] : 0.f};
+}
+// (mean, rstd) of the row a wave holds as v[i] = quad lane + 64 i (zero outside the row): slot sums in slot order, the xor butterfly,
+// then the centred squares.  A macro, not a function: behind a call boundary the compiler moved the variance blocks out of line
+// (taken branches in every wave; the encoder's residual LayerNorm measured 27.3 -> 28.3 us).  It declares `mean` and `rstd` in the
+// caller's scope.  (Tried: a __forceinline__ function taking the array by reference.  Not tried: a lambda, the array in a struct.)
+#define LN_WAVE_STATS(v, MAXV, lane, nv, C, eps, mean, rstd)                                                                        \
+    float mean, rstd;                                                                                                               \
+    {                                                                                                                               \
+        float s_ = 0.f;                                                                                                             \
+        _Pragma("unroll") for (int i_ = 0; i_ < MAXV; ++i_) s_ += v[i_][0] + v[i_][1] + v[i_][2] + v[i_][3];                        \
+        mean = wave_sum(s_) / (float)C;                                                                                             \
+        float q_ = 0.f;                                                                                                             \
+        _Pragma("unroll") for (int i_ = 0; i_ < MAXV; ++i_) {                                                                       \
+            if (lane + i_ * 64 < nv) {                                                                                              \
+                _Pragma("unroll") for (int k_ = 0; k_ < 4; ++k_) {                                                                  \
+                    const float d_ = v[i_][k_] - mean;                                                                              \
+                    { /* (product rounded, then added - never contracted: the chained LayerNorm must round like the plain one in  \
+                          every instantiation; left to the compiler the f32 kernels fused it and the bf16 ones did not) */         \
+                        _Pragma("clang fp contract(off)") q_ += d_ * d_;                                                            \
+                    }                                                                                                               \
+                }                                                                                                                   \
+            }                                                                                                                       \
+        }                                                                                                                           \
+        rstd = rsqrtf(wave_sum(q_) / (float)C + eps);                                                                               \
+    }
+// Quad idx of the row that starts at element `row_at`: y = affine (+ GELU) of v, then every output that is given - T(y + add), y as
+// float, the float row itself (the residual sum), y as T
+template <typename T>
+__device__ __forceinline__ void ln_finish(f32x4 v, float mean, float rstd, f32x4 g, f32x4 b, int act, f32x4 add, long long row_at, int idx,
+                                          T* out_T2, float* out_f32, float* out_sum, T* out_T) {
+    f32x4 y;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) y[k] = ln_affine(v[k], mean, rstd, g[k], b[k]);
+    if (act == L4P_ACT_GELU) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) y[k] = gelu_for<T>(y[k]);
+    }
+    if (out_T2) {
+        f32x4 y2;
+#pragma unroll
+        for (int k = 0; k < 4; ++k) y2[k] = y[k] + add[k];
+        Vec4<T>::store(ln_quad_at(out_T2 + row_at, idx), (const float*)&y2);
+    }
+    if (out_f32) ((f32x4*)(out_f32 + row_at))[idx] = y;
+    if (out_sum) ((f32x4*)(out_sum + row_at))[idx] = v;
+    if (out_T) Vec4<T>::store(ln_quad_at(out_T + row_at, idx), (const float*)&y);
+}
+
+// One wave per row, MAXV float4 slots per lane.
+// XT: the input row is stored as T (the bf16 engine's activations) instead of float - half the bytes in; it may alias
+// out_T (a wave holds its row in registers before it stores anything).
+// (More rows per wave, all requested before the first is reduced, measured on the 1M x 352 LayerNorm + GELU of the tracker: 1 row
+//  556 us, 2 rows 696 us, 4 rows 889 us - that launch is VALU-bound (GELU on 369 M elements), not latency-bound.)
+// RES: the row normalised is x[row % x_mod] + delta[row] (delta in the engine dtype): the tracker's "keys += attention
+// output; keys = LayerNorm(keys)" (sam/transformer.py:183-185) with the sum formed HERE instead of in the projection's
+// epilogue - the float key stream is read once by this kernel instead of read + written by the GEMM and read again.
+// out_sum (may alias x when x_mod = 0): the float sum itself - the encoder's pre-norm residual stream, where y is only the next
+// linear's input.  PART: the addend is pbias + nsplit float partials [nsplit][M][C] of a split-K projection instead of delta.
+template <typename T, int MAXV, bool XT = false, bool RES = false, bool PART = false>
 __global__ __launch_bounds__(256) void layernorm_kernel(const float* x, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, float eps, T* out_T, float* out_f32, int M,
                                                         int C, const float* __restrict__ add, int add_mod, T* out_T2, int act,
-                                                        const T* __restrict__ delta = nullptr, int x_mod = 0,
-                                                        const float* __restrict__ x_shared = nullptr, int x_period = 1,
-                                                        int x_split = 0, float* out_sum = nullptr,
-                                                        const float* __restrict__ part = nullptr, int nsplit = 0,
-                                                        const float* __restrict__ pbias = nullptr, float* __restrict__ out_stats = nullptr) {
+                                                        const T* __restrict__ delta, int x_mod, const float* __restrict__ x_shared,
+                                                        int x_period, int x_split, float* out_sum, const float* __restrict__ part,
+                                                        int nsplit, const float* __restrict__ pbias, float* __restrict__ out_stats) {
     // (x and the outputs are NOT restrict-qualified: the tracker normalises its key stream and the up-scaled activation in
     //  place; a wave has its whole row in registers - every store depends on the row statistics - before it writes)
     const int lane = threadIdx.x & 63;
-    const int row0 = (blockIdx.x * 4 + (threadIdx.x >> 6)) * ROWS;
-    if (row0 >= M) return;
+    const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (row >= M) return;
     const int nv = C >> 2;
-    // every load of the rows is issued up front (x, gamma, beta, the optional addend): ONE exposed memory round trip per
+    // every load of the row is issued up front (x, gamma, beta, the optional addend): ONE exposed memory round trip per
     // wave instead of three dependent ones (x -> statistics -> gamma/beta/add) - the kernel is latency-, not bandwidth-bound
-    f32x4 v[ROWS][MAXV], g[MAXV], bb[MAXV], av[ROWS][MAXV];
+    f32x4 v[MAXV], g[MAXV], bb[MAXV], av[MAXV];
     const f32x4 z = {0.f, 0.f, 0.f, 0.f};
+    // (RES, x_shared: rows p = row % x_period >= x_split come from the shared set x_shared[p - x_split] - the part of the
+    //  tracker's key stream that is still the same for every track)
+    const int prow = RES && x_shared ? row % x_period : 0;
+    const f32x4* xr = RES && x_shared && prow >= x_split ? (const f32x4*)(x_shared + (long long)(prow - x_split) * C)
+                                                         : (const f32x4*)(x + (long long)(RES && x_mod > 0 ? row % x_mod : row) * C);
+    const f32x4* ar = out_T2 ? (const f32x4*)(add + (long long)(row % add_mod) * C) : nullptr;
 #pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-        const int row = row0 + r < M ? row0 + r : M - 1;  // (a clamped duplicate row is loaded but never stored)
-        // (RES, x_shared: rows p = row % x_period >= x_split come from the shared set x_shared[p - x_split] - the part of the
-        //  tracker's key stream that is still the same for every track)
-        const int prow = RES && x_shared ? row % x_period : 0;
-        const f32x4* xr = RES && x_shared && prow >= x_split
-                              ? (const f32x4*)(x_shared + (long long)(prow - x_split) * C)
-                              : (const f32x4*)(x + (long long)(RES && x_mod > 0 ? row % x_mod : row) * C);
-        const f32x4* ar = out_T2 ? (const f32x4*)(add + (long long)(row % add_mod) * C) : nullptr;
+    for (int i = 0; i < MAXV; ++i) {
+        const int idx = lane + i * 64;
+        const bool in = idx < nv;
+        if constexpr (XT)
+            v[i] = ln_quad((const T*)x + (long long)row * C, idx, in);
+        else
+            v[i] = in ? xr[idx] : z;
+        if constexpr (PART) {  // the addend is bias + the float partials of a split-K projection, summed in slice order
+            f32x4 d = pbias ? ((const f32x4*)pbias)[in ? idx : 0] : z;
+            // (four slices requested at a time - a slice past the last is a clamped duplicate that is not added: with a plain
+            //  loop over a run-time nsplit every slice was its own memory round trip, 24 in a row per lane at batch 1)
+            for (int sl = 0; sl < nsplit; sl += 4) {
+                f32x4 t[4];
 #pragma unroll
-        for (int i = 0; i < MAXV; ++i) {
-            const int idx = lane + i * 64;
-            const bool in = idx < nv;
-            if (XT && sizeof(T) == 2) {  // (branch-free: the load is clamped, not predicated, so all slots are requested at once)
-                const vec4h<T> t = ((const vec4h<T>*)((const vec4e<T>*)x + (long long)row * C))[in ? idx : 0];
+                for (int u = 0; u < 4; ++u) {
+                    const int su = sl + u < nsplit ? sl + u : sl;
+                    t[u] = ((const f32x4*)(part + ((long long)su * M + row) * C))[in ? idx : 0];
+                }
 #pragma unroll
-                for (int k = 0; k < 4; ++k) v[r][i][k] = in ? (float)t[k] : 0.f;
-            } else {
-                v[r][i] = in ? LN_LD(xr + idx) : z;
-            }
-            if constexpr (RES) {
-#ifdef LN_OLD_PART  // (A/B aid: the round-4 shape - one instantiation, run-time branch, one slice per round trip)
-                if (part) {
-                    f32x4 d = pbias ? ((const f32x4*)pbias)[in ? idx : 0] : z;
-                    for (int sl = 0; sl < nsplit; ++sl) {
-                        const f32x4 t = ((const f32x4*)(part + ((long long)sl * M + row) * C))[in ? idx : 0];
+                for (int u = 0; u < 4; ++u) {
+                    if (sl + u < nsplit) {
 #pragma unroll
-                        for (int k = 0; k < 4; ++k) d[k] += t[k];
+                        for (int k = 0; k < 4; ++k) d[k] += t[u][k];
                     }
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) v[r][i][k] += in ? d[k] : 0.f;
-                } else
-#endif
-                if constexpr (PART) {  // the addend is bias + the float partials of a split-K projection, summed in slice order
-                    f32x4 d = pbias ? ((const f32x4*)pbias)[in ? idx : 0] : z;
-                    // (four slices requested at a time - a slice past the last is a clamped duplicate that is not added: with a plain
-                    //  loop over a run-time nsplit every slice was its own memory round trip, 24 in a row per lane at batch 1)
-                    for (int sl = 0; sl < nsplit; sl += 4) {
-                        f32x4 t[4];
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            const int su = sl + u < nsplit ? sl + u : sl;
-                            t[u] = ((const f32x4*)(part + ((long long)su * M + row) * C))[in ? idx : 0];
-                        }
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) {
-                            if (sl + u < nsplit) {
-#pragma unroll
-                                for (int k = 0; k < 4; ++k) d[k] += t[u][k];
-                            }
-                        }
-                    }
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) v[r][i][k] += in ? d[k] : 0.f;
-                } else if constexpr (sizeof(T) == 2) {
-                    const vec4h<T> t = LN_LD((const vec4h<T>*)((const vec4e<T>*)delta + (long long)row * C) + (in ? idx : 0));
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) v[r][i][k] += in ? (float)t[k] : 0.f;
-                } else {
-                    const f32x4 t = ((const f32x4*)((const float*)delta + (long long)row * C))[in ? idx : 0];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) v[r][i][k] += in ? t[k] : 0.f;
                 }
             }
-            av[r][i] = (in && ar) ? ar[idx] : z;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[i][k] += in ? d[k] : 0.f;
+        } else if constexpr (RES) {
+            const f32x4 d = ln_quad(delta + (long long)row * C, idx, in);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) v[i][k] += d[k];
         }
+        av[i] = (in && ar) ? ar[idx] : z;
     }
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) {
@@ -128,180 +155,29 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* x, const fl
         g[i] = in ? ((const f32x4*)gamma)[idx] : z;
         bb[i] = in ? ((const f32x4*)beta)[idx] : z;
     }
-#pragma unroll
-    for (int r = 0; r < ROWS; ++r) {
-        const int row = row0 + r;
-        if (row >= M) break;
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < MAXV; ++i) s += v[r][i][0] + v[r][i][1] + v[r][i][2] + v[r][i][3];
-        const float mean = wave_sum(s) / (float)C;
-        float q = 0.f;
-#pragma unroll
-        for (int i = 0; i < MAXV; ++i) {
-            if (lane + i * 64 < nv) {
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const float d = v[r][i][k] - mean;
-                    {  // (product rounded, then added - never contracted: the chained LayerNorm must round like the plain one in every
-                       //  instantiation; left to the compiler the f32 kernels fused it and the bf16 ones did not)
-#pragma clang fp contract(off)
-                        q += d * d;
-                    }
-                }
-            }
-        }
-        const float rstd = rsqrtf(wave_sum(q) / (float)C + eps);
-        if constexpr (RES) {  // (mean, rstd) of the row: what layernorm_chain_kernel re-derives this launch's float result from
-            if (out_stats && lane == 0) {
-                out_stats[2ll * row] = mean;
-                out_stats[2ll * row + 1] = rstd;
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < MAXV; ++i) {
-            const int idx = lane + i * 64;
-            if (idx < nv) {
-                f32x4 y;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) y[k] = ln_affine(v[r][i][k], mean, rstd, g[i][k], bb[i][k]);
-                if (act == L4P_ACT_GELU) {
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) y[k] = gelu_for<T>(y[k]);
-                }
-                if (out_T2) {  // T(y + add[row % add_mod]): the "+ positional / + prompt token" operand of the tracker
-                    if (sizeof(T) == 2) {
-                        vec4h<T> o;
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) o[k] = (vec4e<T>)(y[k] + av[r][i][k]);
-                        LN_ST((vec4h<T>*)((vec4e<T>*)out_T2 + (long long)row * C) + idx, o);
-                    } else {
-                        f32x4 o;
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) o[k] = y[k] + av[r][i][k];
-                        ((f32x4*)((float*)out_T2 + (long long)row * C))[idx] = o;
-                    }
-                }
-                if (out_f32) LN_ST((f32x4*)(out_f32 + (long long)row * C) + idx, y);
-                if constexpr (RES) {  // pre-norm residual stream (the encoder): the SUM x + delta is what lives on, y is only xn
-                    if (out_sum) LN_ST((f32x4*)(out_sum + (long long)row * C) + idx, v[r][i]);
-                }
-                if (out_T) {
-                    if (sizeof(T) == 2) {
-                        vec4h<T> o;
-#pragma unroll
-                        for (int k = 0; k < 4; ++k) o[k] = (vec4e<T>)y[k];
-                        LN_ST((vec4h<T>*)((vec4e<T>*)out_T + (long long)row * C) + idx, o);
-                    } else {
-                        ((f32x4*)((float*)out_T + (long long)row * C))[idx] = y;
-                    }
-                }
-            }
+    LN_WAVE_STATS(v, MAXV, lane, nv, C, eps, mean, rstd)
+    if constexpr (RES) {  // (mean, rstd) of the row: what the chained forms re-derive this launch's float result from
+        if (out_stats && lane == 0) {
+            out_stats[2ll * row] = mean;
+            out_stats[2ll * row + 1] = rstd;
         }
     }
-}
-
-template <typename T, int MAXV>
-static void launch_ln_t(const float* x, const float* gamma, const float* beta, float eps, void* out_T, float* out_f32, int M,
-                        int C, const float* add, int add_mod, void* out_T2, int act, hipStream_t stream) {
-    hipLaunchKernelGGL((layernorm_kernel<T, MAXV>), dim3((M + 3) / 4), dim3(256), 0, stream, x, gamma, beta, eps, (T*)out_T, out_f32,
-                       M, C, add, add_mod, (T*)out_T2, act);
-}
-template <typename T>
-static void launch_ln(const float* x, const float* gamma, const float* beta, float eps, void* out_T, float* out_f32, int M, int C,
-                      const float* add, int add_mod, void* out_T2, int act, hipStream_t stream) {
-    // float4 slots per lane: 2 covers C <= 512 (DPT / tracker up-scaling), 6 the 1408-wide streams, 8 the 2048 limit
-    if (C <= 512)
-        launch_ln_t<T, 2>(x, gamma, beta, eps, out_T, out_f32, M, C, add, add_mod, out_T2, act, stream);
-    else if (C <= 1536)
-        launch_ln_t<T, 6>(x, gamma, beta, eps, out_T, out_f32, M, C, add, add_mod, out_T2, act, stream);
-    else
-        launch_ln_t<T, 8>(x, gamma, beta, eps, out_T, out_f32, M, C, add, add_mod, out_T2, act, stream);
-}
-
-int launch_layernorm_ex(int dtype, const float* x, const float* gamma, const float* beta, float eps, void* out_T,
-                        float* out_f32, int M, int C, const float* add, int add_mod, void* out_T2, int act,
-                        hipStream_t stream) {
-    if (C % 4 || C > 2048 || (out_T2 && (!add || add_mod <= 0))) {
-        l4p_set_error("layernorm: C=%d must be a multiple of 4 and <= 2048 (and out_T2 needs add/add_mod)", C);
-        return L4P_E_INVALID;
+#pragma unroll
+    for (int i = 0; i < MAXV; ++i) {
+        const int idx = lane + i * 64;
+        // (RES, out_sum: the pre-norm residual stream of the encoder - the SUM x + delta is what lives on, y is only xn)
+        if (idx < nv) ln_finish<T>(v[i], mean, rstd, g[i], bb[i], act, av[i], (long long)row * C, idx, out_T2, out_f32, RES ? out_sum : nullptr, out_T);
     }
-    ProfScope prof(PROF_LAYERNORM, stream, "M%d C%d add%d T2%d act%d f32%d", M, C, add != nullptr, out_T2 != nullptr, act, out_f32 != nullptr);
-    L4P_WITH_T(dtype, T, launch_ln<T>(x, gamma, beta, eps, out_T, out_f32, M, C, add, add_mod, out_T2, act, stream));
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// (the token-ordered form of the first window's key LayerNorms: key_ln_tracks_kernel below)
-static bool key_ln_tracks_fits(int M, int C, int x_mod, int add_mod, const void* add, const void* out_T, const void* out_T2);
-template <typename T, bool CHAIN, bool XT = false>
-static void launch_key_ln_tracks(const float* xs, int P, const void* dprev, const float* stats_in, const float* g0, const float* b0,
-                                 const void* delta, const float* gamma, const float* beta, float eps, void* out_T, float* out_f32, int M, int C,
-                                 const float* add, void* out_T2, float* out_stats, hipStream_t stream, const float* x_track = nullptr,
-                                 const float* x_half = nullptr, int x_split = 0);
-
-// y = LayerNorm(x[row % x_mod] + delta[row]) with the tracker's outputs (see layernorm_kernel RES); out_sum (may alias x when
-// x_mod = 0): the float sum itself - the encoder's pre-norm residual stream, where y is only the next linear's input;
-// part / nsplit / pbias: the addend is bias + nsplit float partials [nsplit][M][C] of a split-K projection instead of delta
-int launch_layernorm_res(int dtype, const float* x, int x_mod, const void* delta_T, const float* gamma, const float* beta, float eps,
-                         void* out_T, float* out_f32, int M, int C, const float* add, int add_mod, void* out_T2, const float* x_shared,
-                         int x_period, int x_split, hipStream_t stream, float* out_sum, const float* part, int nsplit,
-                         const float* pbias, float* out_stats) {
-    if (part && (nsplit < 1 || nsplit > 16)) {
-        l4p_set_error("layernorm_res: 1 <= nsplit <= 16 slices of float partials");
-        return L4P_E_INVALID;
-    }
-    if (x_shared && (x_period <= 0 || x_split < 0 || x_split > x_period)) {
-        l4p_set_error("layernorm_res: shared rows need 0 <= x_split <= x_period, x_period > 0");
-        return L4P_E_INVALID;
-    }
-    if (!x_shared) x_period = 1, x_split = 0;
-    if (C % 4 || C > 1536 || (!delta_T && !part) || (out_T2 && (!add || add_mod <= 0))) {
-        l4p_set_error("layernorm_res: C=%d must be a multiple of 4 and <= 1536, delta or partials must be given (and out_T2 needs add/add_mod)", C);
-        return L4P_E_INVALID;
-    }
-    ProfScope prof(PROF_LAYERNORM, stream, "M%d C%d res T2%d f32%d", M, C, out_T2 != nullptr, out_f32 != nullptr);
-    if (!part && !out_sum && delta_T && key_ln_tracks_fits(M, C, x_mod, add_mod, add, out_T, out_T2) &&
-        (x_mod > 0 ? !x_shared : (!x_shared || x_period == add_mod))) {
-        if (x_mod > 0) {
-            L4P_WITH_T(dtype, T, (launch_key_ln_tracks<T, false>(x, add_mod, nullptr, nullptr, nullptr, nullptr, delta_T, gamma, beta, eps, out_T,
-                                                                 out_f32, M, C, add, out_T2, out_stats, stream)));
-        } else {  // the tracks' own float rows (possibly normalised in place), the common rows of a half-shared layer from x_shared
-            L4P_WITH_T(dtype, T, (launch_key_ln_tracks<T, false, true>(nullptr, add_mod, nullptr, nullptr, nullptr, nullptr, delta_T, gamma, beta, eps,
-                                                                       out_T, out_f32, M, C, add, out_T2, out_stats, stream, x, x_shared, x_split)));
-        }
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
-    const dim3 grid((M + 3) / 4);
-#define LN_RES_LAUNCH(TT, MV, PT)                                                                                                          \
-    hipLaunchKernelGGL((layernorm_kernel<TT, MV, false, 1, true, PT>), grid, dim3(256), 0, stream, x, gamma, beta, eps, (TT*)out_T, out_f32, M, \
-                       C, add, add_mod, (TT*)out_T2, (int)L4P_ACT_NONE, (const TT*)delta_T, x_mod, x_shared, x_period, x_split, out_sum, part,  \
-                       nsplit, pbias, out_stats)
-    // (the split-K-partials form is its own instantiation: its four-slices-at-a-time requests double the register count, which the
-    //  delta form - the encoder's and the tracker's rows at 8 waves per SIMD - must not pay)
-#ifdef LN_OLD_PART
-    const float* const part_sel = nullptr;
-#else
-    const float* const part_sel = part;
-#endif
-    L4P_WITH_T(dtype, T, {
-        if (C <= 512) {
-            if (part_sel) LN_RES_LAUNCH(T, 2, true); else LN_RES_LAUNCH(T, 2, false);
-        } else {
-            if (part_sel) LN_RES_LAUNCH(T, 6, true); else LN_RES_LAUNCH(T, 6, false);
-        }
-    });
-#undef LN_RES_LAUNCH
-    HIP_TRY(hipGetLastError());
-    return 0;
 }
 
 // Chained key LayerNorm (the tracker's second layer in a FIRST window, sam/transformer.py:183-185): the layer before normalised
 // xs[row % x_mod] + dprev[row] - float rows common to all tracks plus that layer's update in the engine dtype - and stored only its
 // engine-dtype outputs and (mean, rstd) per row.  Its float result, the residual this layer adds to, is re-derived here from those
 // (ln_affine: bit for bit what it would have stored), so the float key master [N * P][C] is neither written nor read: 1.1 GB of
-// 3.7 GB per 64 tracks.  One wave per row, every load issued before the first use, C <= 1536.
+// 3.7 GB per 64 tracks.  One wave per row, every load of the row's operands issued before the first use, C <= 1536.  (Its own kernel
+// beside layernorm_kernel<RES>: it holds two updates instead of one and so reads the four parameter vectors where it uses them.
+// Folded into layernorm_kernel as a CHAIN parameter, with that kernel's up-front gamma / beta, it takes 154 (f16) and 178 (f32)
+// registers against 106 and 128 here: 3 and 2 waves per SIMD instead of 4.)
 template <typename T>
 __global__ __launch_bounds__(256) void layernorm_chain_kernel(const float* __restrict__ xs, int x_mod, const T* __restrict__ dprev,
                                                               const float* __restrict__ stats, const float* __restrict__ g0,
@@ -324,23 +200,10 @@ __global__ __launch_bounds__(256) void layernorm_chain_kernel(const float* __res
         const int idx = lane + i * 64;
         const bool in = idx < nv;
         v[i] = in ? xr[idx] : z;
-        if (sizeof(T) == 2) {
-            const vec4h<T> t = ((const vec4h<T>*)((const vec4e<T>*)dprev + (long long)row * C))[in ? idx : 0];
-            const vec4h<T> u = ((const vec4h<T>*)((const vec4e<T>*)delta + (long long)row * C))[in ? idx : 0];
+        const f32x4 t = ln_quad(dprev + (long long)row * C, idx, in);
+        d1[i] = ln_quad(delta + (long long)row * C, idx, in);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                v[i][k] += in ? (float)t[k] : 0.f;
-                d1[i][k] = in ? (float)u[k] : 0.f;
-            }
-        } else {
-            const f32x4 t = ((const f32x4*)((const float*)dprev + (long long)row * C))[in ? idx : 0];
-            const f32x4 u = ((const f32x4*)((const float*)delta + (long long)row * C))[in ? idx : 0];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                v[i][k] += in ? t[k] : 0.f;
-                d1[i][k] = in ? u[k] : 0.f;
-            }
-        }
+        for (int k = 0; k < 4; ++k) v[i][k] += t[k];
         av[i] = (in && ar) ? ar[idx] : z;
     }
     // the previous layer's float result (its out_f32, had it stored one) + this layer's update
@@ -355,51 +218,13 @@ __global__ __launch_bounds__(256) void layernorm_chain_kernel(const float* __res
             v[i] = z;
         }
     }
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) s += v[i][0] + v[i][1] + v[i][2] + v[i][3];
-    const float mean = wave_sum(s) / (float)C;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < MAXV; ++i) {
-        if (lane + i * 64 < nv) {
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float d = v[i][k] - mean;
-                {  // (product rounded, then added - never contracted: the chained LayerNorm must round like the plain one in every
-                       //  instantiation; left to the compiler the f32 kernels fused it and the bf16 ones did not)
-#pragma clang fp contract(off)
-                        q += d * d;
-                    }
-            }
-        }
-    }
-    const float rstd = rsqrtf(wave_sum(q) / (float)C + eps);
+    LN_WAVE_STATS(v, MAXV, lane, nv, C, eps, mean, rstd)
 #pragma unroll
     for (int i = 0; i < MAXV; ++i) {
         const int idx = lane + i * 64;
-        if (idx < nv) {
-            const f32x4 gg = ((const f32x4*)gamma)[idx], bb = ((const f32x4*)beta)[idx];
-            f32x4 y;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) y[k] = ln_affine(v[i][k], mean, rstd, gg[k], bb[k]);
-            if (out_f32) ((f32x4*)(out_f32 + (long long)row * C))[idx] = y;
-            if (sizeof(T) == 2) {
-                vec4h<T> o, o2;
-#pragma unroll
-                for (int k = 0; k < 4; ++k) o[k] = (vec4e<T>)y[k], o2[k] = (vec4e<T>)(y[k] + av[i][k]);
-                if (out_T) ((vec4h<T>*)((vec4e<T>*)out_T + (long long)row * C))[idx] = o;
-                if (out_T2) ((vec4h<T>*)((vec4e<T>*)out_T2 + (long long)row * C))[idx] = o2;
-            } else {
-                if (out_T) ((f32x4*)((float*)out_T + (long long)row * C))[idx] = y;
-                if (out_T2) {
-                    f32x4 o2;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) o2[k] = y[k] + av[i][k];
-                    ((f32x4*)((float*)out_T2 + (long long)row * C))[idx] = o2;
-                }
-            }
-        }
+        if (idx < nv)
+            ln_finish<T>(v[i], mean, rstd, ((const f32x4*)gamma)[idx], ((const f32x4*)beta)[idx], L4P_ACT_NONE, av[i], (long long)row * C, idx,
+                         out_T2, out_f32, nullptr, out_T);
     }
 }
 // ---------------------------------------------------------------------------------------------
@@ -413,6 +238,9 @@ __global__ __launch_bounds__(256) void layernorm_chain_kernel(const float* __res
 // registers, the parameter vectors ONCE per workgroup into LDS, and the per-track operands of track n + 1 are requested before
 // track n is reduced.  Per-row arithmetic is the row kernels' statement for statement (ln_affine, the uncontracted variance,
 // the same summation order): bit-identical outputs (tests/test_track_gpu.py).
+// This kernel is NOT written on the helpers above: on them (with either store order of the tail) the own-master form normalised in
+// place was 0.7 % slower in three calls (262144 rows: 878.5 -> 885.0, 877.6 -> 882.9, 874.3 -> 880.9 us), so it keeps the body it
+// had, and compiles to the same instructions as before.
 // ---------------------------------------------------------------------------------------------
 // XT (later windows, layernorm_kernel<RES> with x_mod = 0): the float rows are the tracks' own key master x_track[row] (normalised
 // in place when out_f32 aliases it) - or, for tokens p >= x_split of a half-shared layer 0, still the common rows x_half[p - x_split]:
@@ -554,45 +382,6 @@ __global__ __launch_bounds__(256) void key_ln_tracks_kernel(const float* xs, int
         }
     }
 }
-// the token-ordered form applies when every float row is shared with period P = add_mod, both T outputs are wanted and the
-// rows are whole tracks; tracks per wave: 8 (4096 workgroups for 64 tracks of 2048 tokens)
-static bool key_ln_tracks_fits(int M, int C, int x_mod, int add_mod, const void* add, const void* out_T, const void* out_T2) {
-    // (x_mod = 0: the tracks' own float rows; else every float row is shared with the positional rows' period)
-    return knob(KNOB_LN_TRACKS) && (x_mod == 0 || x_mod == add_mod) && add_mod > 0 && add_mod % 4 == 0 && M % add_mod == 0 && C % 4 == 0 &&
-           C <= 1536 && add && out_T && out_T2;
-}
-template <typename T, bool CHAIN, bool XT>
-static void launch_key_ln_tracks(const float* xs, int P, const void* dprev, const float* stats_in, const float* g0, const float* b0,
-                                 const void* delta, const float* gamma, const float* beta, float eps, void* out_T, float* out_f32, int M, int C,
-                                 const float* add, void* out_T2, float* out_stats, hipStream_t stream, const float* x_track, const float* x_half,
-                                 int x_split) {
-    const int N = M / P, tpw = N < 8 ? N : 8;  // (4 / 8 / 16 tracks per wave measure the same: c3 LayerNorm class 6.38 / 6.38 / 6.41 ms)
-    const dim3 grid((P / 4) * ((N + tpw - 1) / tpw));
-    hipLaunchKernelGGL((key_ln_tracks_kernel<T, CHAIN, XT>), grid, dim3(256), (size_t)(CHAIN ? 4 : 2) * C * sizeof(float), stream, xs, P, (const T*)dprev,
-                       stats_in, g0, b0, (const T*)delta, gamma, beta, eps, (T*)out_T, out_f32, N, C, add, (T*)out_T2, out_stats, tpw, x_track,
-                       x_half, x_split);
-}
-
-int launch_layernorm_chain(int dtype, const float* xs, int x_mod, const void* dprev_T, const float* stats, const float* g0, const float* b0,
-                           const void* delta_T, const float* gamma, const float* beta, float eps, void* out_T, float* out_f32, int M, int C,
-                           const float* add, int add_mod, void* out_T2, hipStream_t stream) {
-    if (C % 4 || C > 1536 || x_mod < 1 || !xs || !dprev_T || !stats || !delta_T || (out_T2 && (!add || add_mod <= 0))) {
-        l4p_set_error("layernorm_chain: C=%d must be a multiple of 4 and <= 1536; shared rows, both updates and the statistics are required", C);
-        return L4P_E_INVALID;
-    }
-    ProfScope prof(PROF_LAYERNORM, stream, "M%d C%d chain T2%d f32%d", M, C, out_T2 != nullptr, out_f32 != nullptr);
-    if (key_ln_tracks_fits(M, C, x_mod, add_mod, add, out_T, out_T2)) {
-        L4P_WITH_T(dtype, T, (launch_key_ln_tracks<T, true>(xs, x_mod, dprev_T, stats, g0, b0, delta_T, gamma, beta, eps, out_T, out_f32, M, C, add,
-                                                            out_T2, nullptr, stream)));
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
-    const dim3 grid((M + 3) / 4);
-    L4P_WITH_T(dtype, T, hipLaunchKernelGGL(layernorm_chain_kernel<T>, grid, dim3(256), 0, stream, xs, x_mod, (const T*)dprev_T, stats, g0, b0,
-                                            (const T*)delta_T, gamma, beta, eps, (T*)out_T, out_f32, M, C, add, add_mod, (T*)out_T2));
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
 
 // ---------------------------------------------------------------------------------------------
 // LayerNorm (+ GELU) of SHORT rows stored in the engine dtype, C <= 512 (round 5): the tracker's LayerNorm3d after its first
@@ -601,7 +390,8 @@ int launch_layernorm_chain(int dtype, const float* xs, int x_mod, const void* dp
 // ONE DPP ROW of 16 lanes (lane k holds the quads k, k + 16, ...: 88 quads = 5.5 slots, 92 % of the lanes busy), the statistics are
 // two 4-step rotations inside the DPP row, a wave works on 4 rows at a time and walks RPW / 4 such groups with gamma / beta in
 // registers, the next group's rows requested as soon as the current ones are converted.  Row sums are formed in a different
-// order than layernorm_kernel's: equal to it to float rounding, not bit for bit.
+// order than layernorm_kernel's (and the variance product is left to the compiler to contract): equal to it to float rounding, not
+// bit for bit - the statistics stay this kernel's own.
 // ---------------------------------------------------------------------------------------------
 __device__ __forceinline__ float row16_sum(float v) {
     // rotations inside a row of 16 lanes: every lane ends with the row's sum (same order in every lane's view up to rotation)
@@ -627,13 +417,14 @@ __global__ __launch_bounds__(256) void ln_rows16_kernel(const T* x, const float*
         g[j] = q < nv ? ((const f32x4*)gamma)[q] : z;
         bb[j] = q < nv ? ((const f32x4*)beta)[q] : z;
     }
-    vec4h<T> raw[SLOTS];
+    typedef typename Vec4<T>::raw_t raw_t;
+    raw_t raw[SLOTS];
     auto request = [&](long long row) {
         const long long rr = row < M ? row : M - 1;  // (a clamped duplicate row is loaded but never stored)
 #pragma unroll
         for (int j = 0; j < SLOTS; ++j) {
             const int q = k + 16 * j;
-            raw[j] = ((const vec4h<T>*)((const vec4e<T>*)x + rr * C))[q < nv ? q : 0];
+            raw[j] = ((const raw_t*)(x + rr * C))[q < nv ? q : 0];
         }
     };
     request(row_base + sub);
@@ -668,62 +459,105 @@ __global__ __launch_bounds__(256) void ln_rows16_kernel(const T* x, const float*
             for (int j = 0; j < SLOTS; ++j) {
                 const int q = k + 16 * j;
                 if (q < nv) {
-                    vec4h<T> o;
+                    float o[4];
 #pragma unroll
                     for (int e = 0; e < 4; ++e) {
-                        float y = ln_affine(v[j][e], mean, rstd, g[j][e], bb[j][e]);
-                        if (act == L4P_ACT_GELU) y = gelu_for<T>(y);
-                        o[e] = (vec4e<T>)y;
+                        o[e] = ln_affine(v[j][e], mean, rstd, g[j][e], bb[j][e]);
+                        if (act == L4P_ACT_GELU) o[e] = gelu_for<T>(o[e]);
                     }
-                    ((vec4h<T>*)((vec4e<T>*)out + row * C))[q] = o;
+                    Vec4<T>::store(ln_quad_at(out + row * C, q), o);
                 }
             }
         }
     }
 }
 
-// LayerNorm of rows stored in the engine dtype (bf16 engine: bf16 in, bf16 out, possibly in place; f32 engine: the plain kernel)
-int launch_layernorm_T(int dtype, const void* x_T, const float* gamma, const float* beta, float eps, void* out_T, int M, int C,
-                       int act, hipStream_t stream) {
-    if (!is16(dtype))
-        return launch_layernorm_ex(dtype, (const float*)x_T, gamma, beta, eps, out_T, nullptr, M, C, nullptr, 0, nullptr, act, stream);
-    if (C % 4 || C > 2048) {
-        l4p_set_error("layernorm_T: C=%d must be a multiple of 4 and <= 2048", C);
-        return L4P_E_INVALID;
+// ---- the one launcher: ln_select names the form, this starts it ----
+template <typename T, int MAXV, bool XT, bool RES, bool PART>
+static void launch_ln_row(const LnParams& p, hipStream_t stream) {
+    hipLaunchKernelGGL((layernorm_kernel<T, MAXV, XT, RES, PART>), dim3((p.M + 3) / 4), dim3(256), 0, stream, (const float*)p.x, p.gamma, p.beta,
+                       p.eps, (T*)p.out_T, p.out_f32, p.M, p.C, p.add, p.add_mod, (T*)p.out_T2, p.act, (const T*)p.delta_T, p.x_mod, p.x_shared,
+                       p.x_period, p.x_split, p.out_sum, p.part, p.nsplit, p.pbias, p.out_stats);
+}
+template <typename T, bool XT, bool RES, bool PART>
+static void launch_ln_row_slots(int slots, const LnParams& p, hipStream_t stream) {
+    if (slots == 2) return launch_ln_row<T, 2, XT, RES, PART>(p, stream);
+    if (RES || slots == 6) return launch_ln_row<T, 6, XT, RES, PART>(p, stream);
+    if constexpr (!RES) launch_ln_row<T, 8, XT, RES, PART>(p, stream);
+}
+template <typename T, bool CHAIN, bool XT>
+static void launch_ln_tokens(const LnParams& p, hipStream_t stream) {
+    // tracks per wave: 8 (4096 workgroups for 64 tracks of 2048 tokens; 4 / 8 / 16 measure the same: c3 LayerNorm class 6.38 / 6.38 / 6.41 ms)
+    const int P = p.add_mod, N = p.M / P, tpw = N < 8 ? N : 8;
+    const dim3 grid((P / 4) * ((N + tpw - 1) / tpw));
+    hipLaunchKernelGGL((key_ln_tracks_kernel<T, CHAIN, XT>), grid, dim3(256), (size_t)(CHAIN ? 4 : 2) * p.C * sizeof(float), stream,
+                       XT ? nullptr : (const float*)p.x, P, (const T*)p.dprev_T, p.stats_in, p.g0, p.b0, (const T*)p.delta_T, p.gamma, p.beta, p.eps,
+                       (T*)p.out_T, p.out_f32, N, p.C, p.add, (T*)p.out_T2, p.out_stats, tpw, XT ? (const float*)p.x : nullptr, p.x_shared, p.x_split);
+}
+template <typename T>
+static int launch_ln_form(LnChoice c, const LnParams& p, hipStream_t stream) {
+    switch (c.form) {
+        case LN_ROW: launch_ln_row_slots<T, false, false, false>(c.slots, p, stream); return 0;
+        case LN_ROW_RES: launch_ln_row_slots<T, false, true, false>(c.slots, p, stream); return 0;
+        case LN_ROW_PART: launch_ln_row_slots<T, false, true, true>(c.slots, p, stream); return 0;
+        case LN_ROW_CHAIN:
+            hipLaunchKernelGGL(layernorm_chain_kernel<T>, dim3((p.M + 3) / 4), dim3(256), 0, stream, (const float*)p.x, p.x_mod, (const T*)p.dprev_T,
+                               p.stats_in, p.g0, p.b0, (const T*)p.delta_T, p.gamma, p.beta, p.eps, (T*)p.out_T, p.out_f32, p.M, p.C, p.add, p.add_mod,
+                               (T*)p.out_T2);
+            return 0;
+        case LN_TOKEN_SHARED: launch_ln_tokens<T, false, false>(p, stream); return 0;
+        case LN_TOKEN_OWN: launch_ln_tokens<T, false, true>(p, stream); return 0;
+        case LN_TOKEN_CHAIN: launch_ln_tokens<T, true, false>(p, stream); return 0;
+        case LN_ROW_T:  // rows stored in the engine dtype: the 16-bit types only
+            if constexpr (sizeof(T) == 2) {
+                launch_ln_row_slots<T, true, false, false>(c.slots, p, stream);
+                return 0;
+            }
+            break;
+        case LN_ROWS16:
+            if constexpr (sizeof(T) == 2) {
+                constexpr int RPW = 16;
+                const dim3 grid16((unsigned)(((long long)p.M + 4 * RPW - 1) / (4 * RPW)));
+                auto kern = c.slots == 6 ? ln_rows16_kernel<T, 6, RPW> : ln_rows16_kernel<T, 8, RPW>;
+                hipLaunchKernelGGL(kern, grid16, dim3(256), 0, stream, (const T*)p.x, p.gamma, p.beta, p.eps, (T*)p.out_T, (long long)p.M, p.C, p.act);
+                return 0;
+            }
+            break;
+        default: break;
     }
-    ProfScope prof(PROF_LAYERNORM, stream, "M%d C%d inT act%d", M, C, act);
-    if (knob(KNOB_LN_ROWS16) && C <= 512 && C % 4 == 0 && M >= 4096) {  // short rows, many of them: one DPP row of 16 lanes per row
-        constexpr int RPW = 16;
-        const dim3 grid16((unsigned)(((long long)M + 4 * RPW - 1) / (4 * RPW)));
-        L4P_WITH_T16(dtype, T16, {
-            if (C <= 384)
-                hipLaunchKernelGGL((ln_rows16_kernel<T16, 6, RPW>), grid16, dim3(256), 0, stream, (const T16*)x_T, gamma, beta, eps, (T16*)out_T, (long long)M, C, act);
-            else
-                hipLaunchKernelGGL((ln_rows16_kernel<T16, 8, RPW>), grid16, dim3(256), 0, stream, (const T16*)x_T, gamma, beta, eps, (T16*)out_T, (long long)M, C, act);
-        });
-        HIP_TRY(hipGetLastError());
-        return 0;
+    l4p_set_error("layernorm: no kernel for form %d of dtype %d", (int)c.form, (int)sizeof(T));
+    return L4P_E_INVALID;
+}
+// (the tags key the committed per-shape profiles: they name the entry, not the form)
+static ProfScope ln_prof(LnForm form, hipStream_t stream, const LnParams& p) {
+    switch (form) {
+        case LN_ROW:
+            return ProfScope(PROF_LAYERNORM, stream, "M%d C%d add%d T2%d act%d f32%d", p.M, p.C, p.add != nullptr, p.out_T2 != nullptr, p.act,
+                             p.out_f32 != nullptr);
+        case LN_ROW_T:
+        case LN_ROWS16: return ProfScope(PROF_LAYERNORM, stream, "M%d C%d inT act%d", p.M, p.C, p.act);
+        case LN_ROW_CHAIN:
+        case LN_TOKEN_CHAIN: return ProfScope(PROF_LAYERNORM, stream, "M%d C%d chain T2%d f32%d", p.M, p.C, p.out_T2 != nullptr, p.out_f32 != nullptr);
+        default: return ProfScope(PROF_LAYERNORM, stream, "M%d C%d res T2%d f32%d", p.M, p.C, p.out_T2 != nullptr, p.out_f32 != nullptr);
     }
-    const dim3 grid((M + 3) / 4);
-    const float* xf = (const float*)x_T;  // (re-typed inside the kernel)
-    L4P_WITH_T16(dtype, T16, {
-        if (C <= 512)
-            hipLaunchKernelGGL((layernorm_kernel<T16, 2, true>), grid, dim3(256), 0, stream, xf, gamma, beta, eps, (T16*)out_T,
-                               (float*)nullptr, M, C, (const float*)nullptr, 0, (T16*)nullptr, act);
-        else if (C <= 1536)
-            hipLaunchKernelGGL((layernorm_kernel<T16, 6, true>), grid, dim3(256), 0, stream, xf, gamma, beta, eps, (T16*)out_T,
-                               (float*)nullptr, M, C, (const float*)nullptr, 0, (T16*)nullptr, act);
-        else
-            hipLaunchKernelGGL((layernorm_kernel<T16, 8, true>), grid, dim3(256), 0, stream, xf, gamma, beta, eps, (T16*)out_T,
-                               (float*)nullptr, M, C, (const float*)nullptr, 0, (T16*)nullptr, act);
-    });
-    HIP_TRY(hipGetLastError());
-    return 0;
 }
 
-int launch_layernorm(int dtype, const float* x, const float* gamma, const float* beta, float eps, void* out_T,
-                     float* out_f32, int M, int C, hipStream_t stream) {
-    return launch_layernorm_ex(dtype, x, gamma, beta, eps, out_T, out_f32, M, C, nullptr, 0, nullptr, L4P_ACT_NONE, stream);
+int launch_layernorm(int dtype, const LnParams& p_in, hipStream_t stream) {
+    LnParams p = p_in;
+    if (p.kind == LN_ROWS && p.x_is_T) p.out_f32 = nullptr, p.add = nullptr, p.add_mod = 0, p.out_T2 = nullptr;  // (out_T and act only)
+    if (p.kind != LN_ROWS) p.act = L4P_ACT_NONE;
+    const char* err = nullptr;
+    const LnChoice c = ln_select(dtype, p, LnKnobs{knob(KNOB_LN_TRACKS), knob(KNOB_LN_ROWS16)}, &err);
+    if (c.form == LN_FORM_INVALID) {
+        l4p_set_error(err, p.C);
+        return L4P_E_INVALID;
+    }
+    ProfScope prof = ln_prof(c.form, stream, p);
+    int rc = 0;
+    L4P_WITH_T(dtype, T, rc = launch_ln_form<T>(c, p, stream));
+    if (rc) return rc;
+    HIP_TRY(hipGetLastError());
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------

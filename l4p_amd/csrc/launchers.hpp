@@ -5,21 +5,10 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "ln_select.hpp"
+
 // elementwise.hip
-int launch_layernorm(int dtype, const float* x, const float* gamma, const float* beta, float eps, void* out_T,
-                     float* out_f32, int M, int C, hipStream_t stream);
-int launch_layernorm_ex(int dtype, const float* x, const float* gamma, const float* beta, float eps, void* out_T,
-                        float* out_f32, int M, int C, const float* add, int add_mod, void* out_T2, int act,
-                        hipStream_t stream);
-int launch_layernorm_T(int dtype, const void* x_T, const float* gamma, const float* beta, float eps, void* out_T, int M, int C,
-                       int act, hipStream_t stream);
-int launch_layernorm_res(int dtype, const float* x, int x_mod, const void* delta_T, const float* gamma, const float* beta, float eps,
-                         void* out_T, float* out_f32, int M, int C, const float* add, int add_mod, void* out_T2, const float* x_shared,
-                         int x_period, int x_split, hipStream_t stream, float* out_sum = nullptr, const float* part = nullptr,
-                         int nsplit = 0, const float* pbias = nullptr, float* out_stats = nullptr);
-int launch_layernorm_chain(int dtype, const float* xs, int x_mod, const void* dprev_T, const float* stats, const float* g0, const float* b0,
-                           const void* delta_T, const float* gamma, const float* beta, float eps, void* out_T, float* out_f32, int M, int C,
-                           const float* add, int add_mod, void* out_T2, hipStream_t stream);
+int launch_layernorm(int dtype, const LnParams& p, hipStream_t stream);
 int launch_cast(int dtype, const float* x, void* y, long long n, hipStream_t stream);
 int launch_patch_gather(int dtype, const float* rgb, void* out, int B, int Cin, int T, int H, int W, int pt, int ph,
                         int pw, int Kp, hipStream_t stream);

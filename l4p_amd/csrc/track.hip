@@ -6,84 +6,6 @@
 #include "common.hpp"
 #include "launchers.hpp"
 
-template <typename T> struct Vec8;  // 8 consecutive elements of T as floats
-template <> struct Vec8<bf16_t> {
-    static __device__ __forceinline__ void load(const bf16_t* p, float* v) {
-        const bf16x8 t = *(const bf16x8*)p;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = (float)t[k];
-    }
-    static __device__ __forceinline__ void store(bf16_t* p, const float* v) {
-        bf16x8 t;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) t[k] = (bf16_t)v[k];
-        *(bf16x8*)p = t;
-    }
-};
-template <> struct Vec8<f16_t> {
-    static __device__ __forceinline__ void load(const f16_t* p, float* v) {
-        const f16x8 t = *(const f16x8*)p;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) v[k] = (float)t[k];
-    }
-    static __device__ __forceinline__ void store(f16_t* p, const float* v) {
-        f16x8 t;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) t[k] = (f16_t)v[k];
-        *(f16x8*)p = t;
-    }
-};
-template <> struct Vec8<float> {
-    static __device__ __forceinline__ void load(const float* p, float* v) {
-        const f32x4 a = *(const f32x4*)p, b = *(const f32x4*)(p + 4);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            v[k] = a[k];
-            v[4 + k] = b[k];
-        }
-    }
-    static __device__ __forceinline__ void store(float* p, const float* v) {
-        *(f32x4*)p = (f32x4){v[0], v[1], v[2], v[3]};
-        *(f32x4*)(p + 4) = (f32x4){v[4], v[5], v[6], v[7]};
-    }
-};
-
-template <typename T> struct Vec4;  // 4 consecutive elements (head dims only need % 4 == 0)
-template <> struct Vec4<bf16_t> {
-    static __device__ __forceinline__ void load(const bf16_t* p, float* v) {
-        const bf16x4 t = *(const bf16x4*)p;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = (float)t[k];
-    }
-    static __device__ __forceinline__ void store(bf16_t* p, const float* v) {
-        bf16x4 t;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) t[k] = (bf16_t)v[k];
-        *(bf16x4*)p = t;
-    }
-};
-template <> struct Vec4<f16_t> {
-    static __device__ __forceinline__ void load(const f16_t* p, float* v) {
-        const f16x4 t = *(const f16x4*)p;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = (float)t[k];
-    }
-    static __device__ __forceinline__ void store(f16_t* p, const float* v) {
-        f16x4 t;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) t[k] = (f16_t)v[k];
-        *(f16x4*)p = t;
-    }
-};
-template <> struct Vec4<float> {
-    static __device__ __forceinline__ void load(const float* p, float* v) {
-        const f32x4 a = *(const f32x4*)p;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) v[k] = a[k];
-    }
-    static __device__ __forceinline__ void store(float* p, const float* v) { *(f32x4*)p = (f32x4){v[0], v[1], v[2], v[3]}; }
-};
-
 // -------------------------------------------------------------------------------------------------
 // Prompt tokens (prompt_encoder.py:78-121,196-203,221-232; mask_decoder.py:107-113):
 // tokens[n] = [mask_tok0, mask_tok1, mask_tok2, point PE + label emb, not-a-point, feature + feature emb]

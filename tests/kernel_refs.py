@@ -39,7 +39,8 @@ ATTN_SHAPES = [
     (2, 260, 96, 8),     # hd 12: tail only
 ]
 
-LN_SHAPES = [(37, 352), (2048, 1408), (6, 176)]
+# (C = 1540 is the first width that takes the row kernel's seventh float4 slot per lane, 2048 its limit: the 8-slot instantiations)
+LN_SHAPES = [(37, 352), (2048, 1408), (6, 176), (5, 1540), (6, 2048)]
 LN_ADD_MODS = ["M", 6, 5]  # "M": one addend row per row; 5 does not divide 37 or 2048
 
 HEAD_OUT_VOX = [256 * 3, 1000, 255, 1]

@@ -49,7 +49,7 @@ def check(y, ref, mode, bf16_out):
 
 
 @pytest.mark.parametrize("mode", MODES)
-@pytest.mark.parametrize("M,C", [(2048, 1408), (37, 352), (6, 176)])
+@pytest.mark.parametrize("M,C", [(2048, 1408), (37, 352), (6, 176), (5, 1540), (6, 2048)])
 def test_layernorm(dev, mode, M, C):
     x = rnd((M, C), 1, 3.0) + 0.5
     g, b = rnd((C,), 2) * 0.2 + 1.0, rnd((C,), 3) * 0.1
@@ -60,12 +60,14 @@ def test_layernorm(dev, mode, M, C):
 
 
 @pytest.mark.parametrize("mode", [L4P_BF16, L4P_F16])
-@pytest.mark.parametrize("M,C", [(8192 + 37, 352), (4096, 512), (5000, 64), (4099, 176)])
+@pytest.mark.parametrize("M,C", [(8192 + 37, 352), (4096, 512), (5000, 64), (4099, 176), (5, 1408), (5, 1540), (6, 2048)])
 @pytest.mark.parametrize("act", [ACT_NONE, ACT_GELU])
 def test_layernorm_of_engine_dtype_rows_in_place(dev, knob, mode, M, C, act):
     """l4p_layernorm_t (LayerNorm3d + GELU of the tracker's up-scaling, mask_decoder.py:145-157, on rows stored in the engine
     dtype, in place): the short-row kernel (knob "ln_rows16": one DPP row of 16 lanes per row, four rows per wave at a time,
-    ragged row counts) and the one-wave-per-row kernel against torch on the same rounded rows; the two agree to an output ulp."""
+    ragged row counts) and the one-wave-per-row kernel against torch on the same rounded rows; the two agree to an output ulp.
+    C = 1408, 1540 and 2048 (past the short-row kernel's 512: both knob values run the row kernel): its 6- and 8-slot
+    instantiations over engine-dtype rows, row counts ragged against the four rows of a workgroup."""
     import ctypes as C_
 
     from l4p_amd import _lib

@@ -390,7 +390,7 @@ def test_dynamic_lds_limit_small_then_over_64k_then_small(dev):
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("M,C", R.LN_SHAPES)
 def test_layernorm_ex_vs_float64(dev, mode, M, C):
-    """layernorm_kernel with the tracker's extras: addend periods M, 6 and 5 (5 divides neither 37 nor 2048), GELU applied BEFORE the
+    """layernorm_kernel with the tracker's extras: addend periods M, 6 and 5 (5 divides neither 37 nor 2048; C = 1540 and 2048: the 8-slot instantiations), GELU applied BEFORE the
     addend, every combination of out_T / out_f32 / out_T2 being null or not (out_T2 without out_T included).  M = 37 and 6 are no
     multiple of the four rows a workgroup takes: two guard rows behind every output must keep their sentinel.  out_T of a launch
     with the addend equals the launch without it bit for bit."""
