@@ -28,31 +28,13 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.hpp"
+#include "attn_tile.hpp"
 #include "launchers.hpp"
-
-__device__ __attribute__((aligned(16))) static const unsigned short g_ones_bf16[8] = {0x3F80, 0x3F80, 0x3F80, 0x3F80,
-                                                                                         0x3F80, 0x3F80, 0x3F80, 0x3F80};
-__device__ __attribute__((aligned(16))) static const unsigned short g_ones_f16[8] = {0x3C00, 0x3C00, 0x3C00, 0x3C00,
-                                                                                        0x3C00, 0x3C00, 0x3C00, 0x3C00};
-__device__ __attribute__((aligned(16))) static const float g_ones_f32[4] = {1.f, 1.f, 1.f, 1.f};
-// K-tile chunk holding head dims DH .. DH+7 (all padding) in the deferred-maximum form: dims DH and DH+1 read as 1.0, so
-// the two bf16 halves of -m that sit in the same dims of Q are added to every score by the QK^T MFMA itself
-__device__ __attribute__((aligned(16))) static const unsigned short g_kone_bf16[8] = {0x3F80, 0x3F80, 0, 0, 0, 0, 0, 0};
-__device__ __attribute__((aligned(16))) static const unsigned short g_kone_f16[8] = {0x3C00, 0x3C00, 0, 0, 0, 0, 0, 0};
 
 // SPLIT = 2: the workgroup has 8 waves; waves 0-3 walk the even KV blocks and waves 4-7 the odd ones for the
 // SAME 128 query rows, and the two partial (m, O, denominator) states are merged through LDS at the end.
 // Used when the launch has too few workgroups to put two of them on a CU (batch 1: 256 workgroups), so
 // every SIMD still holds two waves whose MFMA / VALU / wait phases overlap.
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
-
 // QS = 2 ("query split", batch >= 4): the workgroup has 8 waves that cover 256 query rows (waves 0-3 the first 128, waves
 // 4-7 the second) of ONE (batch, head) and SHARE one K / V^T tile ring: a tile is fetched and written into LDS once per 256
 // query rows instead of once per 128 (half the L2 -> LDS bytes and LDS-DMA writes per MFMA), every wave issues 3 LDS-DMA
@@ -75,12 +57,11 @@ __global__ __launch_bounds__(256 * SPLIT * QS) void attn_kernel(const T* __restr
     constexpr int VBYTES = DP * 128;                // KVB * ES == 128: 12 KB
     static_assert(KVB * ES == 128, "V^T tile rows are 128 bytes");
     static_assert(KBYTES % 4096 == 0 && VBYTES % 4096 == 0, "tile = whole LDS-DMA passes of 256 lanes");
-    static_assert(DH < DP && DH % 4 == 0, "one padding row carries the denominator");
+    static_assert(DP == ATTN_DP && KVB == (ES == 2 ? ATTN_KVB16 : ATTN_KVB32) && KBYTES == ATTN_TILE_BYTES, "the launcher's tile constants");
     constexpr int K_IT = KBYTES / 4096, V_IT = VBYTES / 4096;
     // DEFER: the hand-scheduled body keeps a deferred running maximum (see `step`)
     constexpr bool DEFER = HS;
-    constexpr int DT_L = DH / 32, I_L = DH % 32;                       // where the denominator row lands in O^T
-    constexpr int HI_L = (I_L >> 2) & 1, R_L = (I_L & 3) + 4 * (I_L >> 3);
+    typedef AttnPad<DH> Pad;  // where the denominator row lands in O^T, and -m in Q
 
     extern __shared__ __attribute__((aligned(16))) char smem[];
     static_assert(SPLIT == 1 || QS == 1, "KV split and query split are alternatives");
@@ -92,38 +73,18 @@ __global__ __launch_bounds__(256 * SPLIT * QS) void attn_kernel(const T* __restr
     // through the seam (requested by the last two iterations of the current tile) and its Q rows are fetched into Qs by
     // LDS-DMA a few iterations before the end, so a seam costs one barrier instead of a round trip to HBM with every
     // workgroup of the chip fetching its prologue at the same time (measured: ~3.8 us per seam at batch 4).
-#ifdef ATTN_NO_PERSIST
-    constexpr bool PERSIST = false;
-#else
-    // (Only the 8-wave query-split form: the 4-wave form would need 276 registers, i.e. one wave per SIMD.  -DATTN_SEAM_STEP
-    //  goes one step further - the last step of a tile builds the next tile's first scores from Q read out of Qs, so a seam is
-    //  the output store only - but it needs ~10 registers more than the 256 two waves per SIMD leave: hipcc spills pointers
-    //  to scratch inside the steady-state loop; kept for a future hand-allocated form.)
+    // (Only the 8-wave query-split form: the 4-wave form would need 276 registers, i.e. one wave per SIMD.  Whether the launch caps
+    //  the grid so that workgroups really walk more than one tile is attn_select's decision.)
     constexpr bool PERSIST = SPLIT == 1 && QS > 1;
-#endif
-    constexpr int QROWS = 128 * QS, QBYTES = QROWS * DP * ES;
+    constexpr int QROWS = ATTN_QROWS * QS;
+    static_assert(2 * (KBYTES + VBYTES) == ATTN_RING_BYTES && (!PERSIST || QROWS * DP * ES == ATTN_QSTAGE_BYTES), "the launcher's LDS size");
     char* Qs = smem + 2 * (KBYTES + VBYTES);         // [QROWS][DP] (PERSIST only)
 
     const int tid = threadIdx.x & 255, lane = tid & 63;  // thread / wave index inside the group
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lq = lane & 31, hi = lane >> 5;
-    // XCD-aware work mapping: workgroup L runs on XCD L % 8 (observed dispatch order; speed only, not
-    // correctness).  All S/128 query blocks of one (batch, head) are given to the SAME XCD so that head's
-    // K / V^T (786 KB) is fetched into one L2 instead of eight.
-    const int nqb = S / (128 * QS), units = ntiles / nqb;  // units = B * H
-    auto decode = [&](int v, int& bh_, int& qrow0_) {  // tile v -> (batch * H + head, first query row of the tile in its batch item)
-        int unit, qb;
-        if ((units & 7) == 0) {
-            const int xcd = v & 7, j = v >> 3;
-            unit = xcd + 8 * (j / nqb);
-            qb = j % nqb;
-        } else {
-            unit = v / nqb;
-            qb = v % nqb;
-        }
-        bh_ = unit;
-        qrow0_ = (unit / H) * S + qb * (128 * QS);  // row of q / out: batch * S + token
-    };
+    const int nqb = S / QROWS, units = ntiles / nqb;  // units = B * H
+    auto decode = [&](int v, int& bh_, int& qrow0_) { attn_tile_decode<QROWS>(v, nqb, units, H, S, bh_, qrow0_); };
     const int qloc = (QS > 1 ? grp * 128 : 0) + wave * 32 + lq;  // this lane's query row inside the tile
     const int nkb = S / KVB;
 
@@ -140,15 +101,11 @@ __global__ __launch_bounds__(256 * SPLIT * QS) void attn_kernel(const T* __restr
         vones[i] = d == DH;
         vsrc[i] = (const char*)(vt + (long long)d * S) + vchunk * 16;  // + voff + kb*128
     }
-    const char* ones = std::is_same<T, f16_t>::value ? (const char*)g_ones_f16 : ES == 2 ? (const char*)g_ones_bf16 : (const char*)g_ones_f32;
-    // chunk c = tid + 256 i of a K tile is (k-step c / (2 KVB), key (c % (2 KVB)) / 2, half (c & 1) ^ ((key >> 3) & 1))
-    bool kpad[K_IT];
+    const char* ones = attn_ones_chunk<T>();
+    bool kpad[K_IT];  // chunk c = tid + 256 i of a K tile
 #pragma unroll
-    for (int i = 0; i < K_IT; ++i) {
-        const int c = tid + 256 * i, key = (c % (2 * KVB)) >> 1;
-        kpad[i] = DEFER && (c / (2 * KVB)) * 16 + (((c & 1) ^ ((key >> 3) & 1)) << 3) == DH;
-    }
-    const char* kone = std::is_same<T, f16_t>::value ? (const char*)g_kone_f16 : (const char*)g_kone_bf16;
+    for (int i = 0; i < K_IT; ++i) kpad[i] = DEFER && attn_k_chunk_is_pad<KVB, DH>(tid + 256 * i);
+    const char* kone = attn_kone_chunk<T>();
     // QS: the 768 chunks of a tile are spread over 512 lanes: chunk gt (all lanes) + one more for half of the waves (K: chunk
     // 512 + gt from waves 0-3; V^T: chunk gt - 256 from waves 4-7, its first pass being chunks 256 + gt) - 3 requests per wave
     const int gt = threadIdx.x, gwave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -159,6 +116,7 @@ __global__ __launch_bounds__(256 * SPLIT * QS) void attn_kernel(const T* __restr
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int c = i == 0 ? gt : 512 + (gt & 255), key = (c % (2 * KVB)) >> 1;
+            // (attn_k_chunk_is_pad written out: through the function the two query-split kernels get other instruction text)
             qk_pad[i] = DEFER && (c / (2 * KVB)) * 16 + (((c & 1) ^ ((key >> 3) & 1)) << 3) == DH;
             qk_src[i] = (const char*)kt + c * 16;
             const int cv = i == 0 ? 256 + gt : (gt & 255), d = cv >> 3, slot = cv & 7;
@@ -298,12 +256,11 @@ __global__ __launch_bounds__(256 * SPLIT * QS) void attn_kernel(const T* __restr
     // tile DMA below), so S = K Q^T comes out of the MFMA as score - m_run and P = exp2(S) needs no subtraction.  m_run
     // starts at 0 and is set by the first block.
     float m_run = DEFER ? 0.f : -INFINITY;
-    constexpr int KS_P = DH / 16, HI_P = (DH / 8) & 1;  // k-step / lane half whose Q fragment holds dims DH .. DH+7
-    static_assert(DH % 8 == 0, "the first padding chunk starts at DH");
 
     // K tile row read by this lane for score-tile row i = lq: swap bits 2 and 3
     const int krow = (lq & ~12) | ((lq & 4) << 1) | ((lq & 8) >> 1);
-    // byte offsets of this lane's fragments inside the tiles
+    // byte offsets of this lane's fragments inside the tiles (these, issue_q and the deferred maximum's arithmetic below are written
+    // here and in attention64.hip: as functions of attn_tile.hpp the same expressions compile to other instruction text)
     int koff[NST];
 #pragma unroll
     for (int t = 0; t < NST; ++t) {
@@ -344,21 +301,14 @@ __global__ __launch_bounds__(256 * SPLIT * QS) void attn_kernel(const T* __restr
     //   iteration j:  [ S_{j+1} = K_{j+1} Q^T  (MFMA)  ||  P_j = exp2(S_j*c - m)  (VALU) ]
     //                 [ O^T += V_j^T P_j^T     (MFMA)  ||  row max of S_{j+1}     (VALU) ]
     // so each MFMA batch has independent VALU work to issue under it.  K runs one block ahead of V in the LDS rings.
-#ifdef ATTN_SEAM_STEP
-    if (first_tile)  // (later tiles: s_a and mx come out of the previous tile's last step)
-#endif
-    {
-        __syncthreads();  // K_0 / V_0 / K_1 (and, past the first tile, Q in Qs) have landed; the previous tile's reads are done
-#ifndef ATTN_SEAM_STEP
-        if (!first_tile) {
-            q_from_lds();
-            q_prescale();
-        }
-#endif
-        qk_tile(Ks, s_a);
-        mx = row_max(s_a);
-        __syncthreads();  // every wave has read K_0 before the first iteration re-stages its slot
+    __syncthreads();  // K_0 / V_0 / K_1 (and, past the first tile, Q in Qs) have landed; the previous tile's reads are done
+    if (!first_tile) {
+        q_from_lds();
+        q_prescale();
     }
+    qk_tile(Ks, s_a);
+    mx = row_max(s_a);
+    __syncthreads();  // every wave has read K_0 before the first iteration re-stages its slot
 
     // one pipeline step; HAS_NEXT is a compile-time flag so that the steady-state body is ONE basic block in which the
     // scheduler is free to interleave the two MFMA batches with the VALU work (the last block is peeled)
@@ -368,16 +318,16 @@ __global__ __launch_bounds__(256 * SPLIT * QS) void attn_kernel(const T* __restr
     // maximum exceeds it by more than RESCALE_THR (P <= 2^THR otherwise), and always at the first block.  The block body
     // has no multiply-add in front of the exponential.
     constexpr float RESCALE_THR = 8.f;
-    // SEAM (compile time): the last step of a tile that has a successor - its "next" scores are the next tile's first ones
+    // SEAM (compile time, false at every call): the last step of a tile that has a successor would take the next tile's Q here, so
+    // that its "next" scores are the next tile's first ones and a seam is the output store only.  That form needs ~10 registers more
+    // than the 256 two waves per SIMD leave (hipcc spills pointers to scratch inside the steady-state loop) and is not built.  The
+    // flag stays because `step` naming q_from_lds / q_prescale makes it capture those two closures, and the register allocation of
+    // the eight hand-scheduled instantiations rests on that: without it their instruction text changes.
     auto step = [&](int it, auto has_next, auto seam_, f32x16* s_cur, f32x16* s_nxt) __attribute__((always_inline)) {
         constexpr bool HAS_NEXT = decltype(has_next)::value, SEAM = decltype(seam_)::value;
         const int cur = it & 1;
-#ifndef ATTN_DBG_NOLOAD  // (tools/probes/attn_variants.hip: compute-only timing)
-#ifdef ATTN_DMA_IN_SLOTS_ALL  // (probe)
-        constexpr bool DMA_IN_SLOTS = HS;
-#else
         constexpr bool DMA_IN_SLOTS = HS && SPLIT > 1;  // measured: +4 % for the KV-split (batch 1) form, -2 % otherwise
-#endif
+#ifndef ATTN_DBG_NOLOAD  // (tools/probes/attn_probe.hip: compute-only timing)
         if (!DMA_IN_SLOTS) {
             // (K_{it} in ring slot cur and V_{it-1} in slot cur^1 were consumed last iteration)  Past the end of this tile the
             // rings carry on with the next tile's first blocks (nit is even: its block j lands in slot j & 1 as well)
@@ -387,10 +337,6 @@ __global__ __launch_bounds__(256 * SPLIT * QS) void attn_kernel(const T* __restr
             else if (has_next_tile) issue_v(tvn, 0, cur ^ 1);
             if (PERSIST && has_next_tile && it == nit - 4) issue_q(qrow0n, bhn);
         }
-#endif
-#ifdef ATTN_DBG_NOCOMPUTE  // (probe: staging-only timing)
-        __syncthreads();
-        return;
 #endif
         if constexpr (DEFER) {
             // (mx = row maximum of s_cur, relative to m_run)  The rare side path: move the reference, rescale O, rewrite
@@ -408,9 +354,9 @@ __global__ __launch_bounds__(256 * SPLIT * QS) void attn_kernel(const T* __restr
                         for (int r = 0; r < 16; ++r) o[dt][r] *= alpha;
                 }
                 m_run = m_new;
-                if (hi == HI_P) {
-                    qf[KS_P][0] = -m_hi;
-                    qf[KS_P][1] = -m_lo;
+                if (hi == Pad::HI_P) {
+                    qf[Pad::KS_P][0] = -m_hi;
+                    qf[Pad::KS_P][1] = -m_lo;
                 }
 #pragma unroll
                 for (int t = 0; t < NST; ++t)
@@ -437,10 +383,7 @@ __global__ __launch_bounds__(256 * SPLIT * QS) void attn_kernel(const T* __restr
             // requested after its operand are outstanding); PRE reads run ahead.  Behind every MFMA sits a slice of the
             // block's VALU work: the exp2 / bf16 packing of P_j under the QK MFMAs, the row max of S_{j+1} under the PV ones.
             typedef __attribute__((ext_vector_type(2))) float f32x2;
-#ifndef ATTN_HS_PRE
-#define ATTN_HS_PRE 6
-#endif
-            constexpr int PRE = ATTN_HS_PRE;  // fragment reads in flight ahead of the MFMA that consumes them
+            constexpr int PRE = 6;  // fragment reads in flight ahead of the MFMA that consumes them
             constexpr int NR = HAS_NEXT ? 24 : 12, R0 = HAS_NEXT ? 0 : 12;  // the last block has no next scores to build
             const unsigned lds_k = (unsigned)(size_t)(__attribute__((address_space(3))) char*)Ks;
             const unsigned lds_v = (unsigned)(size_t)(__attribute__((address_space(3))) char*)Vs;
@@ -603,12 +546,7 @@ __global__ __launch_bounds__(256 * SPLIT * QS) void attn_kernel(const T* __restr
         }
         if (it + 2 == nit) {
             step(it, std::true_type{}, std::false_type{}, s_a, s_b);
-#ifdef ATTN_SEAM_STEP  // (experiment: the last step of a tile also builds the next tile's first scores - see the note at PERSIST)
-            if (PERSIST && has_next_tile)
-                step(it + 1, std::true_type{}, std::integral_constant<bool, PERSIST>{}, s_b, s_a);  // leaves the next tile's first scores in s_a
-            else
-#endif
-                step(it + 1, std::false_type{}, std::false_type{}, s_b, s_a);
+            step(it + 1, std::false_type{}, std::false_type{}, s_b, s_a);
         } else {
             step(it, std::false_type{}, std::false_type{}, s_a, s_b);  // (a single KV block: never persistent)
         }
@@ -638,20 +576,14 @@ __global__ __launch_bounds__(256 * SPLIT * QS) void attn_kernel(const T* __restr
     }
 
     // ---- normalise and store: lane owns query q_row, d = 32*dt + (r&3) + 8*(r>>2) + 4*hi -------------
-    float l_tot = o[DT_L][R_L];
+    float l_tot = o[Pad::DT_L][Pad::R_L];
     {
         const float other = __shfl_xor(l_tot, 32);
-        if (hi != HI_L) l_tot = other;
+        if (hi != Pad::HI_L) l_tot = other;
     }
     const float inv = 1.0f / l_tot;
     T* op = out + (long long)q_row * ((long long)H * DH) + (long long)h * DH;
-#ifndef ATTN_NO_WIDE_STORE
     if constexpr (ES == 2) {
-        // The row is split across the half-waves in 4-column pieces (lane: columns 8k + 4hi .. + 3 of every 8-column group
-        // k).  One v_permlane32_swap per dword of a group PAIR (k, k+1) hands the upper half's group-k piece down and the
-        // lower half's group-(k+1) piece up: lanes 0-31 then hold columns 8k .. 8k+7, lanes 32-63 columns 8k+8 .. 8k+15 ->
-        // one 16-byte store per pair instead of two 8-byte ones (the store tail is bound by the number of store
-        // instructions, not by bytes).
         constexpr int NG = DH / 8;
         u32x2 pk[NG];
 #pragma unroll
@@ -661,104 +593,61 @@ __global__ __launch_bounds__(256 * SPLIT * QS) void attn_kernel(const T* __restr
             for (int e = 0; e < 4; ++e) v[e] = (vec4e<T>)(o[k >> 2][4 * (k & 3) + e] * inv);
             pk[k] = __builtin_bit_cast(u32x2, v);
         }
+        attn_store_row16(op, pk, hi);
+    } else {
 #pragma unroll
-        for (int k = 0; k + 1 < NG; k += 2) {
-            const auto x = __builtin_amdgcn_permlane32_swap(pk[k][0], pk[k + 1][0], false, false);
-            const auto y = __builtin_amdgcn_permlane32_swap(pk[k][1], pk[k + 1][1], false, false);
-            *(u32x4*)(op + 8 * k + 8 * hi) = (u32x4){x[0], y[0], x[1], y[1]};
-        }
-        if constexpr (NG & 1) *(u32x2*)(op + 8 * (NG - 1) + 4 * hi) = pk[NG - 1];
-        continue;  // next tile
-    }
-#endif
+        for (int dt = 0; dt < NDT; ++dt)
 #pragma unroll
-    for (int dt = 0; dt < NDT; ++dt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const int d0 = dt * 32 + 8 * g + 4 * hi;
-            if (d0 < DH) {
-                if (ES == 2) {
-                    vec4h<T> v;
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) v[k] = (vec4e<T>)(o[dt][4 * g + k] * inv);
-                    *(vec4h<T>*)(op + d0) = v;
-                } else {
-                    *(f32x4*)(op + d0) = (f32x4){o[dt][4 * g] * inv, o[dt][4 * g + 1] * inv, o[dt][4 * g + 2] * inv,
-                                                 o[dt][4 * g + 3] * inv};
-                }
+            for (int g = 0; g < 4; ++g) {
+                const int d0 = dt * 32 + 8 * g + 4 * hi;
+                if (d0 < DH)
+                    *(f32x4*)(op + d0) = (f32x4){o[dt][4 * g] * inv, o[dt][4 * g + 1] * inv, o[dt][4 * g + 2] * inv, o[dt][4 * g + 3] * inv};
             }
-        }
+    }
     }  // tile loop
 }
 
-template <typename T, int KVB, int DH, int SPLIT, bool HS = false, int QS = 1>
-static int launch_attn_t(const void* q, const void* kt, const void* vt, void* out, int B, int S, int H, float scale,
-                         hipStream_t stream) {
-    constexpr int DP = 96;
-    const int ntiles = (S / (128 * QS)) * H * B;
-    // query-split form: persistent workgroups (one 8-wave workgroup per CU) that walk the tiles with the next tile's operands
-    // prefetched across the seam; the Q staging buffer sits behind the tile rings
-    const int persist_env = knob(KNOB_ATTN_PERSIST);
-    const bool persist = SPLIT == 1 && QS > 1 && persist_env && S / KVB >= 4 && (S / KVB) % 2 == 0;  // (the kernel's PERSIST)
-    const int slots = 256;  // one 8-wave workgroup per CU (250 registers: two waves per SIMD)
-    const int grid = persist && ntiles > slots ? slots : ntiles;
-    const size_t lds = SPLIT * 2 * (size_t)(DP / 16 * KVB * 2 * 8 * sizeof(T) + DP * 128) + (QS > 1 ? (size_t)128 * QS * DP * sizeof(T) : 0);
-    auto kern = attn_kernel<T, DP, KVB, DH, SPLIT, HS, QS>;
+// ---- launching: the form attn_select names, in the instantiation of (dtype, head dim) ----
+template <typename T, int DH, int SPLIT, bool HS = false, int QS = 1>
+static int launch_attn_t(const AttnChoice& c, const void* q, const void* kt, const void* vt, void* out, int S, int H, hipStream_t stream) {
+    auto kern = attn_kernel<T, ATTN_DP, sizeof(T) == 2 ? ATTN_KVB16 : ATTN_KVB32, DH, SPLIT, HS, QS>;
     static lds_attr_state attr_done;
-    HIP_TRY(lds_attr_once(attr_done, kern, (int)lds));
-    // scale == 0 (L4P_ATTN_PRESCALED): q already carries head_dim^-0.5 * log2(e); the kernels then multiply by exactly 1
-    const float c_scale = scale > 0.f ? scale * 1.4426950408889634f : 1.0f;
-    // which form ran (include/l4p_hip.h, at l4p_prof_detail): the tests assert it; formatted only while profiling is on
-    const char* form = sizeof(T) == 4 ? "f32"
-                       : QS > 1       ? (grid < ntiles ? "qsplit persist" : "qsplit pertile")
-                       : SPLIT > 1    ? (HS ? "kvsplit" : "kvsplit cs")
-                                      : (HS ? "unsplit" : "unsplit cs");
-    ProfScope prof(PROF_ATTENTION, stream, "B%d S%d H%d Dh%d %s", B, S, H, DH, form);
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256 * SPLIT * QS), lds, stream, (const T*)q, (const T*)kt, (const T*)vt, (T*)out,
-                       S, H, c_scale, ntiles);
+    HIP_TRY(lds_attr_once(attr_done, kern, c.lds_bytes));
+    hipLaunchKernelGGL(kern, dim3(c.grid), dim3(c.block), c.lds_bytes, stream, (const T*)q, (const T*)kt, (const T*)vt, (T*)out, S, H,
+                       c.c_scale, c.ntiles);
+    return 0;
+}
+// (Dh is 88 or 64: attn_select has refused everything else)
+#define ATTN_LAUNCH(T, ...) \
+    (Dh == 88 ? launch_attn_t<T, 88, __VA_ARGS__>(c, q, kt, vt, out, S, H, stream) : launch_attn_t<T, 64, __VA_ARGS__>(c, q, kt, vt, out, S, H, stream))
+
+int launch_attn_form(int dtype, const AttnChoice& c, const void* q, const void* kt, const void* vt, void* out, int B, int S, int H, int Dh,
+                     hipStream_t stream) {
+    ProfScope prof(PROF_ATTENTION, stream, "B%d S%d H%d Dh%d %s", B, S, H, Dh, attn_form_tag(c));  // (formatted only while profiling is on)
+    int rc = L4P_E_INVALID;
+    switch (c.form) {
+        case ATTN_F32: rc = ATTN_LAUNCH(float, 1); break;
+        case ATTN_UNSPLIT: L4P_WITH_T16(dtype, T16, rc = ATTN_LAUNCH(T16, 1, true)); break;
+        case ATTN_UNSPLIT_CS: L4P_WITH_T16(dtype, T16, rc = ATTN_LAUNCH(T16, 1)); break;
+        case ATTN_KVSPLIT: L4P_WITH_T16(dtype, T16, rc = ATTN_LAUNCH(T16, 2, true)); break;
+        case ATTN_KVSPLIT_CS: L4P_WITH_T16(dtype, T16, rc = ATTN_LAUNCH(T16, 2)); break;
+        case ATTN_QSPLIT: L4P_WITH_T16(dtype, T16, rc = launch_attn_t<T16, 88, 1, true, 2>(c, q, kt, vt, out, S, H, stream)); break;
+        case ATTN_ROWS64: rc = launch_attn_rows64(dtype, c, q, kt, vt, out, S, H, Dh, stream); break;
+        default: l4p_set_error("attention: no kernel form %d", (int)c.form); break;
+    }
+    if (rc) return rc;
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
-template <typename T16>
-static int launch_attention16(int variant, bool split, const void* q, const void* kt, const void* vt, void* out, int B, int S, int H,
-                              int Dh, float scale, hipStream_t stream) {
-    if (variant != 1) {
-        // query split (8 waves share the K / V^T tiles): when the launch still fills the chip with 256-row workgroups, two per CU
-        const bool qsplit = !split && S % 256 == 0 && (long long)(S / 256) * H * B >= 512 && variant != 2;
-        if (Dh == 88 && qsplit) return launch_attn_t<T16, 64, 88, 1, true, 2>(q, kt, vt, out, B, S, H, scale, stream);
-        if (Dh == 88)
-            return split ? launch_attn_t<T16, 64, 88, 2, true>(q, kt, vt, out, B, S, H, scale, stream)
-                         : launch_attn_t<T16, 64, 88, 1, true>(q, kt, vt, out, B, S, H, scale, stream);
-        return split ? launch_attn_t<T16, 64, 64, 2, true>(q, kt, vt, out, B, S, H, scale, stream)
-                     : launch_attn_t<T16, 64, 64, 1, true>(q, kt, vt, out, B, S, H, scale, stream);
-    }
-    if (Dh == 88)
-        return split ? launch_attn_t<T16, 64, 88, 2>(q, kt, vt, out, B, S, H, scale, stream)
-                     : launch_attn_t<T16, 64, 88, 1>(q, kt, vt, out, B, S, H, scale, stream);
-    return split ? launch_attn_t<T16, 64, 64, 2>(q, kt, vt, out, B, S, H, scale, stream)
-                 : launch_attn_t<T16, 64, 64, 1>(q, kt, vt, out, B, S, H, scale, stream);
-}
-
-// scale = Dh^-0.5 (reference :150)
-int launch_attention(int dtype, const void* q, const void* kt, const void* vt, void* out, int B, int S, int H, int Dh,
-                     float scale, hipStream_t stream) {
-    if (S % 128 || (Dh != 88 && Dh != 64) || !(scale >= 0.f)) {
-        l4p_set_error("attention: need S %% 128 == 0, head_dim in {88, 64} and scale >= 0 (S=%d Dh=%d scale=%g)", S, Dh, (double)scale);
+int launch_attention(int dtype, const void* q, const void* kt, const void* vt, void* out, int B, int S, int H, int Dh, float scale,
+                     hipStream_t stream) {
+    const AttnKnobs knobs = {knob(KNOB_ATTN_VARIANT), knob(KNOB_ATTN_PERSIST), knob(KNOB_ATTN64)};
+    const char* err = "";
+    const AttnChoice c = attn_select(dtype, B, S, H, Dh, scale, knobs, &err);
+    if (c.form == ATTN_FORM_INVALID) {
+        l4p_set_error(err, S, Dh, (double)scale);
         return L4P_E_INVALID;
     }
-    // too few workgroups for two per CU (256 CUs): split the KV range over two wave groups inside each workgroup
-    const bool split = (long long)(S / 128) * H * B < 512 && (S / 64) % 2 == 0;
-    int variant = knob(KNOB_ATTN_VARIANT);  // tuning aid: 1 = compiler-scheduled body
-    // bf16 with the scale inside: the hand-scheduled bodies fold scale * log2(e) into their Q fragments, a second bf16 rounding of
-    // q (2^-9 per element) that shifts the scores of a large-norm query row against large-norm keys by a few percent of a unit -
-    // measured 2.7e-2 of max|out| on a row of 8x norm against keys of 6x norm.  The compiler-scheduled body applies the scale in
-    // float to the accumulated scores.  (The engine passes pre-scaled q and is not affected.)
-    if (dtype == L4P_BF16 && scale > 0.f) variant = 1;
-    // chip-filling 16-bit launches: one wave per SIMD, 64 query rows per wave (attention64.hip)
-    if (is16(dtype) && variant == 0 && knob(KNOB_ATTN64) && S % 256 == 0 && (S / 64) % 2 == 0 && S / 64 >= 4 && (long long)(S / 256) * H * B >= 256)
-        return launch_attention64(dtype, q, kt, vt, out, B, S, H, Dh, scale, stream);
-    if (is16(dtype)) L4P_WITH_T16(dtype, T16, return launch_attention16<T16>(variant, split, q, kt, vt, out, B, S, H, Dh, scale, stream));
-    if (Dh == 88) return launch_attn_t<float, 32, 88, 1>(q, kt, vt, out, B, S, H, scale, stream);
-    return launch_attn_t<float, 32, 64, 1>(q, kt, vt, out, B, S, H, scale, stream);
+    return launch_attn_form(dtype, c, q, kt, vt, out, B, S, H, Dh, stream);
 }

@@ -20,12 +20,12 @@
 #include <cstdlib>
 #include <type_traits>
 
-#include "common.hpp"
+#include "attn_tile.hpp"
 #include "launchers.hpp"
 
 namespace attn64 {
 
-#ifdef ATTN64_TRACE  // (tools/probes/attn64_probe.hip: s_memtime stamps of wave 0 of workgroup 0 at the phase boundaries of a KV step)
+#ifdef ATTN64_TRACE  // (tools/probes/attn_probe.hip: s_memtime stamps of wave 0 of workgroup 0 at the phase boundaries of a KV step)
 __device__ long long g_trace[4096];
 #define A64_STAMP(slot)                                                                    \
     do {                                                                                   \
@@ -46,21 +46,6 @@ __device__ long long g_trace[4096];
     do {                  \
     } while (0)
 #endif
-
-// the two constant pieces of a tile (attention.hip): row DH of V^T reads ones (the denominator comes out of the MFMA), head dims DH, DH+1
-// of K read 1.0 (they meet the two halves of -m in Q's padding)
-__device__ __attribute__((aligned(16))) static const unsigned short g_ones_bf16[8] = {0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80};
-__device__ __attribute__((aligned(16))) static const unsigned short g_ones_f16[8] = {0x3C00, 0x3C00, 0x3C00, 0x3C00, 0x3C00, 0x3C00, 0x3C00, 0x3C00};
-__device__ __attribute__((aligned(16))) static const unsigned short g_kone_bf16[8] = {0x3F80, 0x3F80, 0, 0, 0, 0, 0, 0};
-__device__ __attribute__((aligned(16))) static const unsigned short g_kone_f16[8] = {0x3C00, 0x3C00, 0, 0, 0, 0, 0, 0};
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
 
 __device__ __forceinline__ unsigned pack2(float a, float b, bf16_t) {
     typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
@@ -86,14 +71,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     typedef typename Frag<T>::type frag_t;
     typedef const __attribute__((address_space(1))) void* gptr_t;
     typedef __attribute__((address_space(3))) void* lptr_t;
-    constexpr int DP = 96, KVB = 64, ES = 2, QB = 2;
+    constexpr int DP = ATTN_DP, KVB = ATTN_KVB16, ES = 2, QB = 2;
     constexpr int NKS = DP / 16, NST = KVB / 32, NDT = DP / 32;  // 6 k-steps, 2 score tiles, 3 output d tiles
     constexpr int KBYTES = NKS * KVB * 2 * 8 * ES, VBYTES = DP * 128;  // 12 KB each
     constexpr int K_IT = KBYTES / 4096, V_IT = VBYTES / 4096;
-    constexpr int QROWS = 128 * QB, QBYTES = QROWS * DP * ES;
-    constexpr int DT_L = DH / 32, I_L = DH % 32, HI_L = (I_L >> 2) & 1, R_L = (I_L & 3) + 4 * (I_L >> 3);  // the denominator row of O^T
-    constexpr int KS_P = DH / 16, HI_P = (DH / 8) & 1;  // k-step / lane half whose Q fragment holds dims DH .. DH+7
-    static_assert(DH % 8 == 0 && DH < DP, "the first padding chunk starts at DH and carries -m / the denominator");
+    constexpr int QROWS = ATTN_QROWS2;
+    static_assert(sizeof(T) == ES && 2 * (KBYTES + VBYTES) == ATTN_RING_BYTES && QROWS * DP * ES == ATTN_QSTAGE_BYTES, "the launcher's LDS size");
+    constexpr int DT_L = AttnPad<DH>::DT_L, HI_L = AttnPad<DH>::HI_L, R_L = AttnPad<DH>::R_L;  // the denominator row of O^T
+    constexpr int KS_P = AttnPad<DH>::KS_P, HI_P = AttnPad<DH>::HI_P;  // k-step / lane half whose Q fragment holds dims DH .. DH+7
     constexpr int NP = QB * NST * 16 / 2;  // 32 pairs of scores per lane and KV block
     constexpr int E = ATTN64_EARLY;        // pairs exponentiated one phase early
     constexpr float RESCALE_THR = 8.f;
@@ -107,19 +92,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lq = lane & 31, hi = lane >> 5;
     const int nqb = S / QROWS, units = ntiles / nqb;  // units = B * H
-    auto decode = [&](int v, int& bh_, int& qrow0_) __attribute__((always_inline)) {  // (XCD-aware: all query blocks of one (batch, head) on one XCD, attention.hip)
-        int unit, qb;
-        if ((units & 7) == 0) {
-            const int xcd = v & 7, j = v >> 3;
-            unit = xcd + 8 * (j / nqb);
-            qb = j % nqb;
-        } else {
-            unit = v / nqb;
-            qb = v % nqb;
-        }
-        bh_ = unit;
-        qrow0_ = (unit / H) * S + qb * QROWS;
-    };
+    auto decode = [&](int v, int& bh_, int& qrow0_) __attribute__((always_inline)) { attn_tile_decode<QROWS>(v, nqb, units, H, S, bh_, qrow0_); };
     const int nkb = S / KVB;
 
     // ---- LDS-DMA: every request is (wave-uniform 64-bit base) + (one lane-constant 32-bit offset) --------------------------------
@@ -129,15 +102,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     const unsigned k_lane = tid * 16;
     const int vrow0 = tid >> 3, vslot = tid & 7;
     const unsigned v_lane = (unsigned)(vrow0 * S * ES) + ((vslot ^ ((vrow0 >> 1) & 7)) * 16);
-    const char* ones = std::is_same<T, f16_t>::value ? (const char*)g_ones_f16 : (const char*)g_ones_bf16;
-    const char* kone = std::is_same<T, f16_t>::value ? (const char*)g_kone_f16 : (const char*)g_kone_bf16;
-    bool kpad2, vone2;
-    {
-        const int c = tid + 512, key = (c % (2 * KVB)) >> 1;
-        kpad2 = (c / (2 * KVB)) * 16 + (((c & 1) ^ ((key >> 3) & 1)) << 3) == DH;
-        vone2 = vrow0 + 64 == DH;
-        static_assert(DH >= 64 && DH - 64 < 32, "the constant pieces sit in the third pass of the tile copy");
-    }
+    const char* ones = attn_ones_chunk<T>();
+    const char* kone = attn_kone_chunk<T>();
+    const bool kpad2 = attn_k_chunk_is_pad<KVB, DH>(tid + 512), vone2 = vrow0 + 64 == DH;
+    static_assert(DH >= 64 && DH - 64 < 32, "the constant pieces sit in the third pass of the tile copy");
     // (bhx = batch * H + head of the tile the operands belong to: wave-uniform, kept scalar by the callers)
     auto issue_k = [&](int bhx, int kb, int buf) __attribute__((always_inline)) {
         const char* base = (const char*)kt + ((long long)bhx * nkb + kb) * KBYTES;
@@ -178,7 +146,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
     unsigned pw[NP];      // P of the block the next step multiplies with V^T, packed pairs; filled early for p < E
     float mx[QB] = {0.f, 0.f};
 
-    // fragment addresses (lane-constant)
+    // fragment addresses (lane-constant; as attention.hip's, and like issue_q above and the deferred maximum's arithmetic in `step` written
+    // out in both kernels: through functions of attn_tile.hpp the same expressions compile to other instruction text)
     const int krow = (lq & ~12) | ((lq & 4) << 1) | ((lq & 8) >> 1);
     int koff[NST];
 #pragma unroll
@@ -552,13 +521,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
             for (int k = 0; k < NG; ++k)
                 pk[k] = (u32x2){pack2(o_get(b, k >> 2, 4 * (k & 3)) * inv, o_get(b, k >> 2, 4 * (k & 3) + 1) * inv, T{}),
                                 pack2(o_get(b, k >> 2, 4 * (k & 3) + 2) * inv, o_get(b, k >> 2, 4 * (k & 3) + 3) * inv, T{})};
-#pragma unroll
-            for (int k = 0; k + 1 < NG; k += 2) {
-                const auto x = __builtin_amdgcn_permlane32_swap(pk[k][0], pk[k + 1][0], false, false);
-                const auto y = __builtin_amdgcn_permlane32_swap(pk[k][1], pk[k + 1][1], false, false);
-                *(u32x4*)(op + 8 * k + 8 * hi) = (u32x4){x[0], y[0], x[1], y[1]};
-            }
-            if constexpr (NG & 1) *(u32x2*)(op + 8 * (NG - 1) + 4 * hi) = pk[NG - 1];
+            attn_store_row16(op, pk, hi);
         }
         A64_STAMP(first_tile ? 3 : 7);
     }  // tile loop
@@ -566,31 +529,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1))) voi
 
 }  // namespace attn64
 
-// scale as launch_attention (0 = q pre-scaled by head_dim^-0.5 * log2(e)); S % 256 == 0, S / 64 even and >= 4
-template <typename T>
-static int launch_attn64_t(const void* q, const void* kt, const void* vt, void* out, int B, int S, int H, int Dh, float scale, hipStream_t stream) {
-    const float c_scale = scale > 0.f ? scale * 1.4426950408889634f : 1.0f;
-    const int ntiles = (S / 256) * H * B;
-    const int grid = ntiles > 256 ? 256 : ntiles;
-    const size_t lds = 2 * (size_t)(12288 + 12288) + (size_t)256 * 96 * 2;
-    ProfScope prof(PROF_ATTENTION, stream, "B%d S%d H%d Dh%d rows64", B, S, H, Dh);
-    if (Dh == 88) {
-        auto kern = attn64::attn64_kernel<T, 88>;
-        static lds_attr_state attr_done;
-        HIP_TRY(lds_attr_once(attr_done, kern, (int)lds));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, (const T*)q, (const T*)kt, (const T*)vt, (T*)out, S, H, c_scale, ntiles);
-    } else {
-        auto kern = attn64::attn64_kernel<T, 64>;
-        static lds_attr_state attr_done;
-        HIP_TRY(lds_attr_once(attr_done, kern, (int)lds));
-        hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, stream, (const T*)q, (const T*)kt, (const T*)vt, (T*)out, S, H, c_scale, ntiles);
-    }
-    HIP_TRY(hipGetLastError());
+// the ATTN_ROWS64 arm of launch_attn_form (attention.hip), which holds the profiler scope: grid, block, LDS size and c_scale are the choice's
+template <typename T, int DH>
+static int launch_attn64_t(const AttnChoice& c, const void* q, const void* kt, const void* vt, void* out, int S, int H, hipStream_t stream) {
+    auto kern = attn64::attn64_kernel<T, DH>;
+    static lds_attr_state attr_done;
+    HIP_TRY(lds_attr_once(attr_done, kern, c.lds_bytes));
+    hipLaunchKernelGGL(kern, dim3(c.grid), dim3(c.block), c.lds_bytes, stream, (const T*)q, (const T*)kt, (const T*)vt, (T*)out, S, H, c.c_scale,
+                       c.ntiles);
     return 0;
 }
 
-int launch_attention64(int dtype, const void* q, const void* kt, const void* vt, void* out, int B, int S, int H, int Dh, float scale,
+int launch_attn_rows64(int dtype, const AttnChoice& c, const void* q, const void* kt, const void* vt, void* out, int S, int H, int Dh,
                        hipStream_t stream) {
-    L4P_WITH_T16(dtype, T16, return launch_attn64_t<T16>(q, kt, vt, out, B, S, H, Dh, scale, stream));
+    L4P_WITH_T16(dtype, T16, return Dh == 88 ? launch_attn64_t<T16, 88>(c, q, kt, vt, out, S, H, stream)
+                                             : launch_attn64_t<T16, 64>(c, q, kt, vt, out, S, H, stream));
     return 0;
 }

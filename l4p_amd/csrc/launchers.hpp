@@ -5,6 +5,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "attn_select.hpp"
 #include "ln_select.hpp"
 
 // elementwise.hip
@@ -13,10 +14,13 @@ int launch_cast(int dtype, const float* x, void* y, long long n, hipStream_t str
 int launch_patch_gather(int dtype, const float* rgb, void* out, int B, int Cin, int T, int H, int W, int pt, int ph,
                         int pw, int Kp, hipStream_t stream);
 
-// attention.hip, attention64.hip
+// attention.hip: attn_select (attn_select.hpp) decides, launch_attn_form launches the form it names under one profiler tag
 int launch_attention(int dtype, const void* q, const void* kt, const void* vt, void* out, int B, int S, int H, int Dh, float scale,
                      hipStream_t stream);
-int launch_attention64(int dtype, const void* q, const void* kt, const void* vt, void* out, int B, int S, int H, int Dh, float scale,
+int launch_attn_form(int dtype, const AttnChoice& c, const void* q, const void* kt, const void* vt, void* out, int B, int S, int H, int Dh,
+                     hipStream_t stream);
+// attention64.hip: the ATTN_ROWS64 arm of launch_attn_form (16-bit dtype, Dh 88 / 64)
+int launch_attn_rows64(int dtype, const AttnChoice& c, const void* q, const void* kt, const void* vt, void* out, int S, int H, int Dh,
                        hipStream_t stream);
 
 // dpt_ops.hip

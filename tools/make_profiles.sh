@@ -53,7 +53,7 @@ python tools/rocprof_summary.py $(find $O/prof_${TAG}_c2 -name "*.db" | head -1)
 # one wave owns the SIMD (tools/probes/gap_probe.hip); the 16-bit drift gates' ratios with the non-bit-identical kernels off one by one
 ( for v in 0 1; do echo "== attn64=$v, random operands"; L4P_ATTN64=$v python tools/attn_time.py 2>/dev/null | tail -3; echo "== attn64=$v, all-zero operands"; L4P_ATTN64=$v python tools/attn_time.py --zeros 2>/dev/null | tail -3; done ) > $O/${TAG}_attention64_ab.txt 2>&1
 [ -x tools/probes/gap_probe ] && timeout 300 tools/probes/gap_probe > $O/${TAG}_mfma_gap_probe.txt 2>&1
-[ -x tools/probes/attn64_var_trace ] && ( timeout 60 tools/probes/attn64_var_trace 4; timeout 60 tools/probes/attn64_var_trace 4 1 ) > $O/${TAG}_attention64_step_trace.txt 2>&1
+[ -x tools/probes/attn64_var_trace ] && ( timeout 60 tools/probes/attn64_var_trace 4; timeout 60 tools/probes/attn64_var_trace 4 --zeros ) > $O/${TAG}_attention64_step_trace.txt 2>&1
 bash tools/drift_report.sh > $O/${TAG}_bf16_drift_ratios.txt 2>&1
 # round 6, one of eight ranks of configs[4]: its query shard's tracker kernel by kernel, with this round's token-side forms on / off, the
 # rank's timeline (decoders beside the tracker) and the decoders' CU mask

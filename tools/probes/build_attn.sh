@@ -1,8 +1,8 @@
 #!/bin/bash
-# Ablation builds of the attention kernel (tools/probes/attn_variants.hip): tools/probes/attn_var_<name>
+# Ablation builds of the attention kernels of csrc/attention.hip (tools/probes/attn_probe.hip): tools/probes/attn_var_<name> [batch] ["form"] [--zeros]
 cd "$(dirname "$0")/../.."
 set -e
-build() { /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -amdgpu-mfma-vgpr-form=1 -I include -I l4p_amd/csrc "${@:2}" tools/probes/attn_variants.hip -o tools/probes/attn_var_$1 & }
+build() { /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -amdgpu-mfma-vgpr-form=1 -I include -I l4p_amd/csrc "${@:2}" tools/probes/attn_probe.hip -o tools/probes/attn_var_$1 & }
 build base
 build noload -DATTN_DBG_NOLOAD
 build noexp -DATTN_DBG_NOEXP

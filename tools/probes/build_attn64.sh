@@ -1,7 +1,7 @@
 #!/bin/bash
-# Ablation / trace builds of the 64-rows-per-wave attention kernel: tools/probes/attn64_var_<name>
+# Ablation / trace builds of the 64-rows-per-wave attention kernel (tools/probes/attn_probe.hip): tools/probes/attn64_var_<name> [batch] ["form"] [--zeros]
 cd "$(dirname "$0")/../.."
-build() { /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -amdgpu-mfma-vgpr-form=1 -I include -I l4p_amd/csrc "${@:2}" tools/probes/attn64_probe.hip -o tools/probes/attn64_var_$1 & }
+build() { /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -amdgpu-mfma-vgpr-form=1 -I include -I l4p_amd/csrc -DATTN_PROBE_BATCH=4 "${@:2}" tools/probes/attn_probe.hip -o tools/probes/attn64_var_$1 & }
 build base
 build trace -DATTN64_TRACE
 build noload -DATTN64_DBG_NOLOAD
