@@ -9,6 +9,9 @@ free viewpoint) on the GPU, along an orbit camera path, as a video under DIR.  -
 in the reference) adds the camray task as well and combines depth, flow and pose across time: per-pixel 3D motion in the world frame
 and the flow split into its camera-induced and its object part (l4p_amd.utils.scene_flow), as .npz, consistency numbers as .json and
 an [RGB | flow | camera-compensated flow] video; with --view4d the 4D video is rendered once more, coloured by 3D speed.
+--static-map DIR (this project's own as well) adds the camray task and fuses the clip's per-frame point clouds into ONE voxel map of
+the static scene (l4p_amd.utils.static_map): a PLY of the voxels seen in at least two frames and outside the motion mask, and its
+counters as .json.
 
   python demo/demo.py --videos a.mp4 b.mp4 --ckpt weights/l4p_depth_flow_2d3dtrack_camray_dynseg_v1.ckpt   # needs mediapy
   python demo/demo.py --synthetic                      # no checkpoint / video files here: seeded weights + a seeded video
@@ -16,6 +19,7 @@ an [RGB | flow | camera-compensated flow] video; with --view4d the 4D video is r
   python demo/demo.py --synthetic --recon4d out/       # + 4D point clouds / track trails / frusta as PLY under out/
   python demo/demo.py --synthetic --view4d out/        # + the 4D result from a free viewpoint (.mp4 with mediapy, PNG frames without)
   python demo/demo.py --synthetic --scene-flow out/    # + scene flow / camera-compensated flow (.npz, .json, video) under out/
+  python demo/demo.py --synthetic --static-map out/    # + one fused voxel map of the static scene (.ply, .json) under out/
   python demo/demo.py --davis DAVIS_ROOT --ckpt ...    # JPEGImages/480p/<seq>, Annotations/480p/<seq>: queries on the instance masks
   python demo/demo.py --dycheck DYCHECK_ROOT --ckpt ... --recon4d out/   # <seq>/dense/images, <seq>/calibration.txt
   python demo/demo.py --synthetic --davis X --vis out/ # a small seeded DAVIS (or --dycheck: DyCheck) tree in a temporary directory
@@ -71,6 +75,9 @@ def parse_args(argv=None):
                     help="also run the camray task and write each video's dense scene flow, rigid and camera-compensated flow "
                          "(<seq_name>_sceneflow.npz), their consistency numbers (.json) and an RGB | flow | compensated-flow video "
                          "(l4p_amd.utils.scene_flow) under DIR; with --view4d also <seq_name>_4d_motion, the 4D video coloured by 3D speed")
+    ap.add_argument("--static-map", default=None, metavar="DIR", dest="static_map",
+                    help="also run the camray task and fuse each video's per-frame point clouds into one voxel map of the static scene "
+                         "(<seq_name>_static_map.ply, its counters as .json; l4p_amd.utils.static_map.generate_static_map) under DIR")
     ap.add_argument("--bidirectional", action="store_true",
                     help="track every query in both time directions (estimation_directions [1, -1] on the tracker head and the dataset): "
                          "the frames before a query are estimated by a second tracker pass over the time-flipped clip")
@@ -93,8 +100,8 @@ def parse_args(argv=None):
 def plan(args):
     """(tasks, dataset keyword arguments) of the reference demo's section that ``args`` selects."""
     tasks = ["depth", "flow_2d_backward", "dyn_mask", "track_2d"]  # demo.py:82,99
-    if args.recon4d or args.view4d or args.dycheck or args.scene_flow:
-        tasks.append("camray")  # the reference's 4D sections (demo.py:116-258) add it; scene flow needs the poses too
+    if args.recon4d or args.view4d or args.dycheck or args.scene_flow or args.static_map:
+        tasks.append("camray")  # the reference's 4D sections (demo.py:116-258) add it; scene flow and the static map need the poses too
     kw = dict(crop_size=(args.frames, 224, 224), estimation_directions=[1, -1] if args.bidirectional else [1],
               track_2d_querry_sampling_spacing=args.spacing)
     if args.davis and (args.recon4d or args.view4d):
@@ -190,6 +197,8 @@ def run(args, model, dataset, tasks):
             view_4d(batch, out, tasks, args.view4d)
         if args.scene_flow:
             scene_flow(batch, out, tasks, args.scene_flow, view4d_dir=args.view4d)
+        if args.static_map:
+            static_map(batch, out, tasks, args.static_map)
 
 
 def vis_2d(batch, out, tasks, out_dir):
@@ -298,6 +307,26 @@ def scene_flow(batch, out, tasks, out_dir, view4d_dir=None):
           f"files {(t2 - t1) * 1e3:.0f} ms -> {name}")
     if view4d_dir:
         view_4d(batch, out, tasks, view4d_dir, colors=sf.motion_colors(res)[0], suffix="_4d_motion")
+
+
+def static_map(batch, out, tasks, out_dir):
+    """The clip's point clouds fused into one voxel map of the static scene (l4p_amd.utils.static_map): <seq>_static_map.ply and
+    <seq>_static_map.json, the GPU part and the file writing timed on their own.  (With --synthetic the seeded weights give arbitrary
+    poses and depths: the files are written, the map means nothing.)"""
+    from l4p_amd.utils import static_map as sm
+
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    res = sm.static_map_from_outputs(batch, out, tasks)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    name = sm.generate_static_map(batch, out, tasks, out_dir, res=res)
+    t2 = time.perf_counter()
+    c = res["counters"]
+    ratio = c["n_used"] / c["n_kept"] if c["n_kept"] else float("nan")
+    print(f"  static map: {c['n_kept']} of {c['n_voxels']} voxels of {float(res['grid'][3]):.3g} kept, {c['n_used']} of {c['n_points']} "
+          f"points used ({c['n_masked']} masked), {ratio:.1f} points per voxel; GPU {(t1 - t0) * 1e3:.1f} ms, files "
+          f"{(t2 - t1) * 1e3:.0f} ms -> {name}")
 
 
 if __name__ == "__main__":

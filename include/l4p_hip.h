@@ -43,7 +43,8 @@ typedef void* l4p_stream; /* hipStream_t */
 typedef struct l4p_engine l4p_engine;
 
 const char* l4p_last_error(void);
-int l4p_abi_version(void); /* 22: dense scene flow and camera-compensated flow (l4p_scene_flow, l4p_scene_flow_summary, l4p_scene_flow_colors);
+int l4p_abi_version(void); /* 23: the static scene map (l4p_static_map_ws_bytes, l4p_static_map_insert, l4p_static_map_count, l4p_static_map_emit);
+                              * 22: dense scene flow and camera-compensated flow (l4p_scene_flow, l4p_scene_flow_summary, l4p_scene_flow_colors);
                               * 21: tracking in both time directions (l4p_time_reverse, l4p_track_bidir_queries, l4p_track_bidir_merge);
                               * 20: the split-K rule of the 3x3x3 conv, stated once for caller and launcher (l4p_conv3d_splitk);
                               * 19: 3D-track metrics, inverse-depth alignment and log-space depth errors (l4p_metric_tracks3d,
@@ -578,6 +579,45 @@ int l4p_scene_flow_summary(l4p_stream stream, const float* scene, const float* c
                            int B, int T, int H, int W, float tau_px, double* ws, double* rows);
 int l4p_scene_flow_colors(l4p_stream stream, const float* scene, const unsigned char* valid, const unsigned char* lut, int B, int T,
                           int H, int W, const float* s_max, unsigned char* colors);
+
+/* ------------------------------------------------------------------------------------------------
+ * Static scene map (csrc/static_map.hip; this project's own, the reference writes one PLY per frame; DESIGN.md "Static scene map"):
+ * the clip's world points fused into one voxel map.  points [M][3] float and colors [M][3] uchar are frame-major as l4p_point_map
+ * writes them, M = T HW, point m belongs to frame m / HW; grid [4] float on the device = (ox, oy, oz, v): origin and voxel size.
+ * Point rule, all f32, every operation rounded on its own.  Point m = (x, y, z) is dropped
+ *   as non-finite  if a coordinate is NaN or +-Inf;
+ *   as masked      else if mask_logit != NULL and mask_logit[m] > 0 (a NaN logit is not > 0), or keep != NULL and keep[m] == 0;
+ *   as out of range else if not (v > 0 and v finite), or if for an axis i = floorf(q), q = (p - o) / v, is not in [-2^20, 2^20 - 1]
+ *                  (a NaN i is not).
+ * Otherwise per axis f = (int)floorf((q - i) * 65536.0f), in [0, 65535], and the voxel key is
+ *   (ix + 2^20) | (iy + 2^20) << 21 | (iz + 2^20) << 42     (63 bits; all ones marks an empty slot).
+ * Per voxel, integers only, so that no result depends on the order of arrival: count, the three sums of f, the three colour sums,
+ * first_point (the smallest m; first_frame = first_point / HW), last_frame, and n_frames, the number of distinct frames with a point
+ * in the voxel.  Table: open addressing on the key with atomicCAS, linear probing from a mix of the key, `capacity` slots of 64
+ * bytes, capacity a power of two <= 2^30; the probe loop ends after `capacity` steps, and a point that found no slot counts in
+ * n_overflow and is in no voxel.  T HW <= 2^24 (the colour sums are 32-bit).
+ * Order: voxels leave by first appearance, ascending first_point, among those kept: n_frames >= min_frames and count >= min_points.
+ * Emitted per kept voxel: xyz [V][3] float, in f64, every operation rounded on its own:
+ *   fx = ((double)sum_fx + 0.5 * (double)count) / ((double)count * 65536.0);   x = (float)((double)ox + ((double)ix + fx) * (double)v)
+ * rgb [V][3] uchar = (2 sum_c + count) / (2 count) in integers (half rounds up); count, n_frames, first_frame, last_frame,
+ * first_point [V] int; key [V] long long.  voxel_id [M] int: the output row of the point's voxel, -1 for a dropped point, a point
+ * without a slot or a filtered voxel.
+ * The three calls share ws (l4p_static_map_ws_bytes(capacity, M) bytes; 0 for sizes the entries refuse) and run in this order:
+ *   insert  clears ws, inserts all points in one launch and then marks the frames, one small launch per frame in stream order
+ *           (that is what counts n_frames);
+ *   count   marks the kept voxels and fills counters [8] unsigned long long on the device = n_points, n_used (points with a key),
+ *           n_nonfinite, n_masked, n_out_of_range, n_voxels, n_kept, n_overflow (n_points = n_used + the three drop counts);
+ *   emit    writes the n_kept rows (n_kept as counted: the caller reads counters back to size them) and voxel_id.
+ * Every entry returns L4P_E_INVALID, with nothing launched, for a size it refuses or a null pointer it needs.
+ * ---------------------------------------------------------------------------------------------- */
+size_t l4p_static_map_ws_bytes(long long capacity, long long M);
+int l4p_static_map_insert(l4p_stream stream, const float* points, const unsigned char* colors, const float* mask_logit,
+                          const unsigned char* keep, const float* grid, int T, int HW, long long capacity, void* ws);
+int l4p_static_map_count(l4p_stream stream, void* ws, int T, int HW, long long capacity, int min_frames, int min_points,
+                         unsigned long long* counters);
+int l4p_static_map_emit(l4p_stream stream, void* ws, const float* grid, int T, int HW, long long capacity, long long n_kept, float* xyz,
+                        unsigned char* rgb, int* count, int* n_frames, int* first_frame, int* last_frame, int* first_point,
+                        long long* key, int* voxel_id);
 
 /* ------------------------------------------------------------------------------------------------
  * Evaluation metrics: what a metrics_module(batch, out, metadata) of L4PLitModule.step computes (l4p/l4p.py:74-78; the reference
