@@ -12,6 +12,9 @@ an [RGB | flow | camera-compensated flow] video; with --view4d the 4D video is r
 --static-map DIR (this project's own as well) adds the camray task and fuses the clip's per-frame point clouds into ONE voxel map of
 the static scene (l4p_amd.utils.static_map): a PLY of the voxels seen in at least two frames and outside the motion mask, and its
 counters as .json.
+--native DIR (this project's own, --videos / --synthetic) carries the dense results from the network's 224 x 224 grid to the pixel
+grid of the decoded video by guided up-sampling on the GPU (l4p_amd.utils.native_res): depth, flow in source pixels, mask logits,
+validity and the mapped tracks as <seq_name>_native.npz; with --vis also the five-panel video at the source resolution.
 
   python demo/demo.py --videos a.mp4 b.mp4 --ckpt weights/l4p_depth_flow_2d3dtrack_camray_dynseg_v1.ckpt   # needs mediapy
   python demo/demo.py --synthetic                      # no checkpoint / video files here: seeded weights + a seeded video
@@ -20,6 +23,7 @@ counters as .json.
   python demo/demo.py --synthetic --view4d out/        # + the 4D result from a free viewpoint (.mp4 with mediapy, PNG frames without)
   python demo/demo.py --synthetic --scene-flow out/    # + scene flow / camera-compensated flow (.npz, .json, video) under out/
   python demo/demo.py --synthetic --static-map out/    # + one fused voxel map of the static scene (.ply, .json) under out/
+  python demo/demo.py --synthetic --native out/ --vis out/   # + depth / flow / mask at the video's own resolution (.npz, video) under out/
   python demo/demo.py --davis DAVIS_ROOT --ckpt ...    # JPEGImages/480p/<seq>, Annotations/480p/<seq>: queries on the instance masks
   python demo/demo.py --dycheck DYCHECK_ROOT --ckpt ... --recon4d out/   # <seq>/dense/images, <seq>/calibration.txt
   python demo/demo.py --synthetic --davis X --vis out/ # a small seeded DAVIS (or --dycheck: DyCheck) tree in a temporary directory
@@ -78,6 +82,12 @@ def parse_args(argv=None):
     ap.add_argument("--static-map", default=None, metavar="DIR", dest="static_map",
                     help="also run the camray task and fuse each video's per-frame point clouds into one voxel map of the static scene "
                          "(<seq_name>_static_map.ply, its counters as .json; l4p_amd.utils.static_map.generate_static_map) under DIR")
+    ap.add_argument("--native", default=None, metavar="DIR",
+                    help="(--videos / --synthetic) write each video's depth, flow (in source pixels), mask logits, validity and tracks at "
+                         "the resolution of the decoded frames (<seq_name>_native.npz; guided up-sampling, l4p_amd.utils.native_res) under "
+                         "DIR; with --vis also the five-panel video at that resolution as <seq_name>_native")
+    ap.add_argument("--synthetic-size", type=int, nargs=2, default=(480, 854), metavar=("H", "W"), dest="synthetic_size",
+                    help="frame size of the seeded --synthetic video (default 480 854)")
     ap.add_argument("--bidirectional", action="store_true",
                     help="track every query in both time directions (estimation_directions [1, -1] on the tracker head and the dataset): "
                          "the frames before a query are estimated by a second tracker pass over the time-flipped clip")
@@ -90,6 +100,8 @@ def parse_args(argv=None):
         ap.error("--videos, --davis and --dycheck are one input each: give one")
     if not args.synthetic and not (args.ckpt and (args.videos or args.davis or args.dycheck)):
         ap.error("--ckpt and one of --videos / --davis / --dycheck (or --synthetic)")
+    if args.native and (args.davis or args.dycheck):
+        ap.error("--native: the --videos / --synthetic flow (VideoDataset.source_clip)")
     if args.query_frame is not None and args.query_frame < 0:
         ap.error("--query-frame: a frame index >= 0")
     if args.spacing is None:
@@ -136,7 +148,7 @@ def main(argv=None):
         model = model.eval()
         if not (args.davis or args.dycheck):
             args.videos = ["synthetic/480p.mp4"]
-            frames = {args.videos[0]: synthetic_video(1, 50, 480, 854)}
+            frames = {args.videos[0]: synthetic_video(1, 50, *args.synthetic_size)}
     else:
         model = prepare_model(model_config_path=args.config, ckpt_path=args.ckpt, max_queries=args.max_queries,
                               precision=precision, accelerator=accelerator)
@@ -168,7 +180,7 @@ def main(argv=None):
 
 def run(args, model, dataset, tasks):
     loader = torch.utils.data.DataLoader(dataset, batch_size=1, shuffle=False)
-    for batch in loader:
+    for index, batch in enumerate(loader):
         if args.query_frame is not None:
             if args.query_frame >= batch["rgb_b3thw"].shape[2]:
                 raise SystemExit(f"--query-frame {args.query_frame}: the clip has {batch['rgb_b3thw'].shape[2]} frames")
@@ -199,6 +211,8 @@ def run(args, model, dataset, tasks):
             scene_flow(batch, out, tasks, args.scene_flow, view4d_dir=args.view4d)
         if args.static_map:
             static_map(batch, out, tasks, args.static_map)
+        if args.native:
+            native(batch, out, tasks, *dataset.source_clip(index), args.native, vis_dir=args.vis)
 
 
 def vis_2d(batch, out, tasks, out_dir):
@@ -327,6 +341,42 @@ def static_map(batch, out, tasks, out_dir):
     print(f"  static map: {c['n_kept']} of {c['n_voxels']} voxels of {float(res['grid'][3]):.3g} kept, {c['n_used']} of {c['n_points']} "
           f"points used ({c['n_masked']} masked), {ratio:.1f} points per voxel; GPU {(t1 - t0) * 1e3:.1f} ms, files "
           f"{(t2 - t1) * 1e3:.0f} ms -> {name}")
+
+
+def native(batch, out, tasks, frames, geometry, out_dir, vis_dir=None):
+    """The dense results at the resolution of the decoded frames (l4p_amd.utils.native_res): <seq>_native.npz (depth, flow in source
+    pixels and mask logits as float16, validity, the mapped tracks), the GPU part and the file writing timed on their own.  With
+    ``vis_dir`` the five-panel video is rendered once more at the source resolution as <seq>_native."""
+    from l4p_amd.utils import native_res as nr
+    from l4p_amd.utils import vis2d
+
+    seq = batch["seq_name"][0]
+    os.makedirs(out_dir, exist_ok=True)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    res = nr.native_resolution_outputs(batch, out, tasks, frames, geometry)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    keys = [k for k in ("depth_est_b1thw", "flow_2d_backward_est_b2thw", "dyn_mask_est_b1thw") if k in res]
+    arrays = {k: res[k].cpu().numpy().astype(np.float16) for k in keys}
+    arrays["native_valid_b1thw"] = res["native_valid_b1thw"].cpu().numpy()
+    if "track_2d_traj_est_bn2t" in res:
+        arrays["track_2d_traj_est_bn2t"] = res["track_2d_traj_est_bn2t"].cpu().numpy()
+    np.savez_compressed(os.path.join(out_dir, seq + "_native.npz"), **arrays)
+    t2 = time.perf_counter()
+    H, W = geometry.src_hw
+    print(f"  native: {len(keys)} fields at {H} x {W} from {geometry.out_hw[0]} x {geometry.out_hw[1]}, valid fraction "
+          f"{float(arrays['native_valid_b1thw'].mean()):.3g}; GPU {(t1 - t0) * 1e3:.1f} ms, files {(t2 - t1) * 1e3:.0f} ms -> "
+          f"{os.path.join(out_dir, seq + '_native.npz')}")
+    if vis_dir:
+        t3 = time.perf_counter()
+        vid = vis2d.render_video_panels(nr.native_batch(batch, frames, geometry), res, tasks)["video"]
+        torch.cuda.synchronize()
+        t4 = time.perf_counter()
+        name = vis2d.write_video(vid.cpu().numpy(), vis_dir, seq + "_native")
+        t5 = time.perf_counter()
+        print(f"  native 2D: {vid.shape[0]} frames of {vid.shape[2] // W} panels at {H} x {W}; GPU render {(t4 - t3) * 1e3:.1f} ms, copy to "
+              f"host and file writing {(t5 - t4) * 1e3:.0f} ms -> {name}")
 
 
 if __name__ == "__main__":

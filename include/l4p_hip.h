@@ -43,7 +43,8 @@ typedef void* l4p_stream; /* hipStream_t */
 typedef struct l4p_engine l4p_engine;
 
 const char* l4p_last_error(void);
-int l4p_abi_version(void); /* 23: the static scene map (l4p_static_map_ws_bytes, l4p_static_map_insert, l4p_static_map_count, l4p_static_map_emit);
+int l4p_abi_version(void); /* 24: results at the video's own resolution (l4p_guided_upsample);
+                              * 23: the static scene map (l4p_static_map_ws_bytes, l4p_static_map_insert, l4p_static_map_count, l4p_static_map_emit);
                               * 22: dense scene flow and camera-compensated flow (l4p_scene_flow, l4p_scene_flow_summary, l4p_scene_flow_colors);
                               * 21: tracking in both time directions (l4p_time_reverse, l4p_track_bidir_queries, l4p_track_bidir_merge);
                               * 20: the split-K rule of the 3x3x3 conv, stated once for caller and launcher (l4p_conv3d_splitk);
@@ -618,6 +619,41 @@ int l4p_static_map_count(l4p_stream stream, void* ws, int T, int HW, long long c
 int l4p_static_map_emit(l4p_stream stream, void* ws, const float* grid, int T, int HW, long long capacity, long long n_kept, float* xyz,
                         unsigned char* rgb, int* count, int* n_frames, int* first_frame, int* last_frame, int* first_point,
                         long long* key, int* voxel_id);
+
+/* ------------------------------------------------------------------------------------------------
+ * Native-resolution results (csrc/upsample.hip; this project's own, the reference stops at 224 x 224; DESIGN.md "Native-resolution
+ * results"): joint bilateral up-sampling (Kopf et al. 2007) of low-resolution fields to the pixel grid of the decoded frames.
+ *   guide_hi    device uint8 [B][Tg][H][W][3]: the decoded source frames
+ *   frame_index device int[T]: source frame of every output frame (stride, mirror padding, temporal crop: the table of
+ *               l4p_clip_resize_normalize); NULL = identity, which needs Tg == T
+ *   guide_lo    device f32 [B][3][T][h][w]: rgb_b3thw as the network saw it (normalised); mean3 / std3: HOST float[3], read at call time
+ *   src         device f32 [B][C][T][h][w]: the low-resolution fields, packed; scale: HOST float[C] or NULL (= all 1)
+ *   out         device f32 [B][C][T][H][W];  valid  device uint8 [B][1][T][H][W]
+ * Geometry: the frame H x W was resized to res_h x res_w with half-pixel centres and cropped at (crop_i0, crop_j0) to h x w.  For the
+ * column X of a full-resolution pixel, in f32, every operation rounded on its own:
+ *   sx = float(res_w) / float(W);   x = (float(X) + 0.5f) * sx - 0.5f - float(crop_j0)
+ * and y likewise from Y, res_h / H and crop_i0.  inside = -0.5 <= x < w - 0.5 and -0.5 <= y < h - 0.5; the window centre is
+ * cx = (int)floorf(x + 0.5f), cy likewise.
+ * Taps: the low-resolution pixels (qx, qy) with |qx - cx| <= radius and |qy - cy| <= radius; a tap outside [0, w) x [0, h) is skipped,
+ * and so is a tap for which any of the C values src[b][c][t][qy][qx] is not finite.
+ * Weights: w_tap = f max(g, range_floor) with
+ *   f = exp(-((x - qx)^2 + (y - qy)^2) / (2 sigma_s^2))    (evaluated as the product of its two one-axis factors)
+ *   g = exp(-|I_hi - I_lo|^2 / (2 sigma_r^2)), the squared distance summed over the three channels,
+ *   I_hi = guide_hi[b][frame_index[t]][Y][X][:] / 255,   I_lo[k] = guide_lo[b][k][t][qy][qx] * std3[k] + mean3[k] (unfused).
+ * range_floor > 0 keeps the sum of the weights positive whenever one tap is usable: a pixel whose colour matches no tap degrades to
+ * the spatial Gaussian.
+ * Result: out[c] = scale[c] (sum w_tap src[c][tap]) / (sum w_tap), f32, the taps added in row-major order of the window (hardware
+ * exp2 with pre-scaled constants; no atomics: two runs give the same bits).
+ * valid = inside and 0 <= frame_index[t] < Tg and at least one tap was usable; where valid is 0 every channel of out is 0 and
+ * nothing is read out of range.
+ * L4P_E_INVALID, with nothing launched: a size < 1, C > 8, radius outside 1..3, sigma_s <= 0 or sigma_r <= 0, range_floor outside
+ * (0, 1], res_h > H or res_w > W (this is an up-sampler), crop_i0 + h > res_h or crop_j0 + w > res_w or a negative crop, Tg != T with
+ * a NULL frame_index, a NULL pointer it needs (all but frame_index and scale).
+ * ---------------------------------------------------------------------------------------------- */
+int l4p_guided_upsample(l4p_stream stream, const unsigned char* guide_hi, const int* frame_index, const float* guide_lo,
+                        const float* mean3, const float* std3, const float* src, const float* scale, int B, int C, int T, int Tg, int H,
+                        int W, int res_h, int res_w, int crop_i0, int crop_j0, int h, int w, int radius, float sigma_s, float sigma_r,
+                        float range_floor, float* out, unsigned char* valid);
 
 /* ------------------------------------------------------------------------------------------------
  * Evaluation metrics: what a metrics_module(batch, out, metadata) of L4PLitModule.step computes (l4p/l4p.py:74-78; the reference

@@ -405,3 +405,15 @@ class VideoDataset(torch.utils.data.Dataset):
         return prepare_clip(frames, self.crop_size, self.resize_size, self.max_frames, self.stride,
                             self.track_2d_querry_sampling_spacing, seq_name=str(os.path.basename(path)),
                             default_sample_size=self.default_sample_size, length_multiply_of=self.length_multiply_of)
+
+    def source_clip(self, index: int):
+        """(frames, geometry) of sample ``index`` for results at the video's own resolution (l4p_amd.utils.native_res): the decoded
+        uint8 frames [T0,H,W,3] on the device after the max_frames cut and the stride, and the ``ClipGeometry`` that ``__getitem__``
+        applies to them (``geometry.frame_index`` indexes into ``frames``)."""
+        from ..utils.native_res import clip_geometry
+
+        frames = self._decode(self.video_paths[index]).to(self.device, non_blocking=True)
+        geometry = clip_geometry(frames.shape[0], frames.shape[1], frames.shape[2], self.crop_size, self.resize_size, self.max_frames,
+                                 self.stride, self.default_sample_size, self.length_multiply_of)
+        frames = frames[: self.max_frames - 1] if self.max_frames is not None else frames
+        return frames[:: self.stride].contiguous(), geometry
