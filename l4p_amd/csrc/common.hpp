@@ -264,9 +264,8 @@ __device__ __forceinline__ float wave_max(float v) {
 // the full-size model asks for later).  
 #include <atomic>
 #include <mutex>
-// The LDS of one gfx950 workgroup, static and dynamic together: the most hipFuncSetAttribute grants.  Launchers that choose a kernel
-// form by its LDS request, or refuse a geometry, compare against this.
-constexpr size_t LDS_DEVICE_LIMIT = 160 * 1024;
+
+#include "device_limits.hpp"  // LDS_DEVICE_LIMIT
 struct lds_attr_state {
     std::atomic<int> set[64] = {};
     std::mutex mu;  // raising the limit is serialised, so a smaller request can never overwrite a larger one
@@ -288,6 +287,12 @@ static inline hipError_t lds_attr_once(lds_attr_state& st, K kern, int lds) {
 
 // host-side error plumbing (defined in api.hip)
 void l4p_set_error(const char* fmt, ...);
+// a launcher's refusal: the text (a printf format, e.g. a form selection's *err) with its arguments
+template <typename... A>
+static inline int l4p_refuse(const char* fmt, A... args) {
+    l4p_set_error(fmt, args...);
+    return L4P_E_INVALID;
+}
 #define HIP_TRY(expr)                                                                  \
     do {                                                                               \
         hipError_t _e = (expr);                                                        \

@@ -7,6 +7,7 @@
 
 #include "attn_select.hpp"
 #include "ln_select.hpp"
+#include "track_select.hpp"
 
 // elementwise.hip
 int launch_layernorm(int dtype, const LnParams& p, hipStream_t stream);
@@ -37,7 +38,9 @@ int launch_rays_to_pose_rot(const float* rays, const float* R, float* out, int B
 int launch_rays_to_pose(const float* rays, const float* K, float* out, int B, int T, int h, int w, int H, int W,
                         hipStream_t stream);
 
-// track.hip
+// track.hip: the tracker's kernels but its output tail.  A launcher that chooses anything calls its *_select (track_select.hpp: form,
+// grid, block, LDS size - pure, checked on the host), refuses with the selection's text, and launches the form it names
+static inline dim3 grid_of(const TrackChoice& c) { return dim3(c.gx, c.gy, c.gz); }
 int launch_track_tokens(const float* queries, const float* labels, const float* pfeat, const float* plabel,
                         const float* gauss, const float* mask_tokens, const float* pe0, const float* pe1,
                         const float* nap, const float* fe0, const float* fe1, float* tokens, int N, int C, int T, int H,
@@ -49,7 +52,6 @@ int launch_fill_rows(float* out, const float* v, long long rows, int C, long lon
 int launch_broadcast_block(void* base, long long off, long long bytes, long long stride, int n, hipStream_t stream);
 int launch_small_attn(int dtype, int kind, const void* q, const void* k, const void* v, void* out, int N, int P, int D,
                       int heads, hipStream_t stream);
-int launch_mask_gather(const float* partial, float* masks, int N, int T, int h, int w, int cpt, hipStream_t stream);
 int launch_i2t_probs(int dtype, const float* s, long long lds_, int pairs, const float* cbias, int rows_per_group, void* p, int ldp,
                      long long M, int heads, int tokens, hipStream_t stream);
 int launch_split_hilo(int dtype, const float* in, void* out, int G, int R, long long C, hipStream_t stream);
@@ -61,13 +63,17 @@ int launch_i2t_delta(int dtype, const void* probs, const void* vt, const float* 
 int launch_t2i_probs(int dtype, const float* scores, long long ld_scores, void* probs, float* stats, int N, int P, int HT, hipStream_t stream);
 int launch_t2i_context(int dtype, const void* probs, const float* stats, const void* keys, void* ctx, int N, int P, int C, int heads,
                        int tokens, long long Rg, int shared_from, hipStream_t stream);
-int launch_mask_product(int dtype, const void* up, const float* hyper, float* masks, int N, long long vox, int Cc,
-                        hipStream_t stream);
-int launch_track_readout(const float* masks, float* traj, float* vis, float* depth, int N, int T, int h, int w, int H,
-                         int W, hipStream_t stream);
 int launch_track_prepare(const float* cur_q, const float* orig_q, int start, int ws, float* q_off, float* labels,
                          unsigned char* valid_t, unsigned char* valid_n, int N, hipStream_t stream);
 int launch_track_commit(const float* w_traj, const float* w_vis, const float* w_depth, const unsigned char* valid_t,
                         const unsigned char* valid_n, float* traj, float* vis, float* depth, int T, int start, int ws,
                         int next_start, int last_window, float* cur_q, float* plabel, const float* new_pfeat, float* pfeat,
                         int* best_out, int N, int C, hipStream_t stream);
+
+// track_readout.hip: the tracker's output tail - hyper-network mask product (LDS-staged or direct: mask_product_select), gather of the
+// mask up-scaling's partial sums, fused read-out (1024-thread or column form, or the LDS refusal: track_readout_select)
+int launch_mask_product(int dtype, const void* up, const float* hyper, float* masks, int N, long long vox, int Cc,
+                        hipStream_t stream);
+int launch_mask_gather(const float* partial, float* masks, int N, int T, int h, int w, int cpt, hipStream_t stream);
+int launch_track_readout(const float* masks, float* traj, float* vis, float* depth, int N, int T, int h, int w, int H,
+                         int W, hipStream_t stream);

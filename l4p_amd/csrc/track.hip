@@ -1,10 +1,13 @@
 // Kernels specific to the SAM-style point tracker (reference sparse_heads.py, sam/*.py).
 // The heavy projections run in gemm.hpp; what lives here is the small-token attention in its three
-// shapes, prompt-token construction, the per-query key initialisation, the hyper-network mask
-// product, the fused (trilinear up-sampling + soft-argmax + spatial means) read-out that never
-// materialises the [N,3,16,224,224] logits, and the integer/boolean sliding-window bookkeeping.
+// shapes, prompt-token construction, the per-query key initialisation, the folded token <-> image
+// attentions and the integer/boolean sliding-window bookkeeping.  The output tail (hyper-network mask
+// product, mask gather, fused read-out) is track_readout.hip.  Which kernel form a launch gets, its
+// grid and its LDS size are decided in track_select.hpp (pure, checked on the host by
+// tests/test_track_select_cpu.py); the launchers at the end of this file check, select and launch.
 #include "common.hpp"
 #include "launchers.hpp"
+#include "track_select.hpp"
 
 // -------------------------------------------------------------------------------------------------
 // Prompt tokens (prompt_encoder.py:78-121,196-203,221-232; mask_decoder.py:107-113):
@@ -204,9 +207,9 @@ __global__ __launch_bounds__(256) void t2i_attn_kernel(const T* __restrict__ q, 
                                                        float scale, long long kv_stride, const float* __restrict__ pre = nullptr,
                                                        long long ld_pre = 0, int heads = 0) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* sc = (float*)smem;      // [6][P]
-    float* qs = sc + 6 * P;        // [6][hd]
-    float* red = qs + 6 * 96;      // [256] scratch, later [ngroups][6][hd]
+    float* sc = (float*)smem;               // [6][P]                    (layout and size: track_select.hpp t2i_attn_lds_bytes)
+    float* qs = sc + t2i_attn_qs_off(P);    // [6][hd], rows 96 floats apart
+    float* red = sc + t2i_attn_red_off(P);  // [256] scratch
     const int n = blockIdx.x, h = blockIdx.y, tid = threadIdx.x;
     const T* qp = q + (long long)n * 6 * D + (long long)h * hd;
     const T* kp = k + (long long)n * kv_stride + (long long)h * hd;  // kv_stride = P*D, or 0 when every query shares K / V
@@ -376,31 +379,22 @@ __global__ __launch_bounds__(256) void t2i_attn_kernel(const T* __restrict__ q, 
 // Image tokens attending to the 6 prompt tokens (cross_attn_image_to_token):
 // q [N][P][D], k, v [N][6][D] -> out [N][P][D].  One thread per (image token, head).
 // -------------------------------------------------------------------------------------------------
+// The arithmetic of one (image token, head), shared by the two kernels below: scores against the six keys, softmax, six-term output.
+// qp: the token's query segment [hd], op: where its result goes (the LDS form passes its LDS tile for both: in place, the thread is
+// the only reader of its segment); kh / vh: the head's segment of the float key / value rows in LDS, rows D floats apart (16-byte
+// aligned: D % 4 == 0 and hd % 4 == 0, so the token rows are read as b128).
 template <typename T>
-__global__ __launch_bounds__(256) void i2t_attn_kernel(const T* __restrict__ q, const T* __restrict__ k,
-                                                       const T* __restrict__ v, T* __restrict__ out, int P, int D, int hd,
-                                                       int heads, float scale, long long q_stride) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* ks = (float*)smem;  // [6][D]
-    float* vs = ks + 6 * D;    // [6][D]
-    const int n = blockIdx.y, tid = threadIdx.x;
-    for (int i = tid; i < 6 * D; i += 256) {
-        ks[i] = (float)k[(long long)n * 6 * D + i];
-        vs[i] = (float)v[(long long)n * 6 * D + i];
-    }
-    __syncthreads();
-    const int work = blockIdx.x * 256 + tid;  // (p, h)
-    if (work >= P * heads) return;
-    const int p = work / heads, h = work % heads;
-    const T* qp = q + (long long)n * q_stride + (long long)p * D + (long long)h * hd;  // q_stride = P*D, or 0 (shared queries)
+__device__ __forceinline__ void i2t_token_head(const T* qp, T* op, const float* kh, const float* vh, int D, int hd, float scale) {
     float s[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
     for (int d0 = 0; d0 < hd; d0 += 4) {
         float qv[4];
         Vec4<T>::load(qp + d0, qv);
 #pragma unroll
-        for (int i = 0; i < 6; ++i)
+        for (int i = 0; i < 6; ++i) {
+            const f32x4 k4 = *(const f32x4*)(kh + i * D + d0);
 #pragma unroll
-            for (int e = 0; e < 4; ++e) s[i] += qv[e] * ks[i * D + h * hd + d0 + e];
+            for (int e = 0; e < 4; ++e) s[i] += qv[e] * k4[e];
+        }
     }
     float m = -INFINITY;
 #pragma unroll
@@ -415,18 +409,38 @@ __global__ __launch_bounds__(256) void i2t_attn_kernel(const T* __restrict__ q, 
         z += s[i];
     }
     const float iz = 1.f / z;
-    T* op = out + ((long long)n * P + p) * D + (long long)h * hd;
     for (int d0 = 0; d0 < hd; d0 += 4) {
-        float o[4];
+        float o[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            float a = 0.f;
+        for (int i = 0; i < 6; ++i) {
+            const f32x4 v4 = *(const f32x4*)(vh + i * D + d0);
 #pragma unroll
-            for (int i = 0; i < 6; ++i) a += s[i] * vs[i * D + h * hd + d0 + e];
-            o[e] = a * iz;
+            for (int e = 0; e < 4; ++e) o[e] += s[i] * v4[e];
         }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) o[e] *= iz;
         Vec4<T>::store(op + d0, o);
     }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void i2t_attn_kernel(const T* __restrict__ q, const T* __restrict__ k,
+                                                       const T* __restrict__ v, T* __restrict__ out, int P, int D, int hd,
+                                                       int heads, float scale, long long q_stride) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    float* ks = (float*)smem;  // [6][D]   (track_select.hpp i2t_attn_kv_bytes)
+    float* vs = ks + 6 * D;    // [6][D]
+    const int n = blockIdx.y, tid = threadIdx.x;
+    for (int i = tid; i < 6 * D; i += 256) {
+        ks[i] = (float)k[(long long)n * 6 * D + i];
+        vs[i] = (float)v[(long long)n * 6 * D + i];
+    }
+    __syncthreads();
+    const int work = blockIdx.x * 256 + tid;  // (p, h)
+    if (work >= P * heads) return;
+    const int p = work / heads, h = work % heads;
+    const T* qp = q + (long long)n * q_stride + (long long)p * D + (long long)h * hd;  // q_stride = P*D, or 0 (shared queries)
+    i2t_token_head<T>(qp, out + ((long long)n * P + p) * D + (long long)h * hd, ks + h * hd, vs + h * hd, D, hd, scale);
 }
 
 // LDS-staged form of i2t_attn_kernel (same arithmetic, same order): a workgroup takes ROWS = 256 / heads consecutive image
@@ -442,7 +456,7 @@ __global__ __launch_bounds__(256) void i2t_attn_lds_kernel(const T* __restrict__
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float* ks = (float*)smem;  // [6][D]
     float* vs = ks + 6 * D;    // [6][D]
-    T* tile = (T*)(smem + ((12 * D * 4 + 15) & ~15));  // [ROWS][D]
+    T* tile = (T*)(smem + i2t_attn_tile_off(D));  // [ROWS][D]
     const int n = blockIdx.y, tid = threadIdx.x;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int rows = 256 / heads, p0 = blockIdx.x * rows;
@@ -460,375 +474,11 @@ __global__ __launch_bounds__(256) void i2t_attn_lds_kernel(const T* __restrict__
     const int pl = tid / heads, h = tid % heads;
     if (pl < nrow) {
         T* qp = tile + (long long)pl * D + (long long)h * hd;
-        float s[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        const float* kh = ks + h * hd;  // (16-byte aligned: D % 4 == 0 and hd % 4 == 0, so the token rows are read as b128)
-        const float* vh = vs + h * hd;
-        for (int d0 = 0; d0 < hd; d0 += 4) {
-            float qv[4];
-            Vec4<T>::load(qp + d0, qv);
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                const f32x4 k4 = *(const f32x4*)(kh + i * D + d0);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) s[i] += qv[e] * k4[e];
-            }
-        }
-        float m = -INFINITY;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            s[i] *= scale;
-            m = fmaxf(m, s[i]);
-        }
-        float z = 0.f;
-#pragma unroll
-        for (int i = 0; i < 6; ++i) {
-            s[i] = expf(s[i] - m);
-            z += s[i];
-        }
-        const float iz = 1.f / z;
-        for (int d0 = 0; d0 < hd; d0 += 4) {
-            float o[4] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int i = 0; i < 6; ++i) {
-                const f32x4 v4 = *(const f32x4*)(vh + i * D + d0);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) o[e] += s[i] * v4[e];
-            }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] *= iz;
-            Vec4<T>::store(qp + d0, o);  // in place: this thread is the only reader of its segment
-        }
+        i2t_token_head<T>(qp, qp, ks + h * hd, vs + h * hd, D, hd, scale);
     }
     __syncthreads();
     char* dst = (char*)(out + ((long long)n * P + p0) * D);
     for (int c = tid; c < chunks; c += 256) *(u32x4*)(dst + (long long)c * 16) = *(const u32x4*)((const char*)tile + c * 16);
-}
-
-// -------------------------------------------------------------------------------------------------
-// masks[n][m][vox] = sum_c hyper[n][m][c] * up[n][vox][c]   (mask_decoder.py:139), up channels-last T.
-// -------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ __launch_bounds__(256) void mask_product_kernel(const T* __restrict__ up, const float* __restrict__ hyper,
-                                                           float* __restrict__ masks, long long vox, int Cc) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* hs = (float*)smem;  // [3][Cc]
-    const int n = blockIdx.y;
-    for (int i = threadIdx.x; i < 3 * Cc; i += 256) hs[i] = hyper[(long long)n * 3 * Cc + i];
-    __syncthreads();
-    for (long long p = blockIdx.x * 256LL + threadIdx.x; p < vox; p += (long long)gridDim.x * 256) {
-        const T* xp = up + ((long long)n * vox + p) * Cc;
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-        for (int c0 = 0; c0 < Cc; c0 += 8) {
-            float x[8];
-            Vec8<T>::load(xp + c0, x);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                a0 += x[e] * hs[c0 + e];
-                a1 += x[e] * hs[Cc + c0 + e];
-                a2 += x[e] * hs[2 * Cc + c0 + e];
-            }
-        }
-        masks[((long long)n * 3 + 0) * vox + p] = a0;
-        masks[((long long)n * 3 + 1) * vox + p] = a1;
-        masks[((long long)n * 3 + 2) * vox + p] = a2;
-    }
-}
-
-// -------------------------------------------------------------------------------------------------
-// Read-out (sparse_heads.py:572-589,645-647) fused: trilinear resize (align_corners=False; identity in
-// time when Tl == T) of the low-res logits [N][3][Tl][h][w] to H x W, then per (n, t):
-//   channel 0 -> soft-argmax xy over H*W with pixel-centre grid (+0.5);  channel 1 -> spatial mean (vis);
-//   channel 2 -> exp(spatial mean) (depth).
-// One workgroup per (n, t); the three low-res maps sit in LDS.
-// -------------------------------------------------------------------------------------------------
-__device__ __forceinline__ void src_idx_nc(int dst, int in, int out, int& i0, int& i1, float& lam) {
-    float src = ((float)in / (float)out) * ((float)dst + 0.5f) - 0.5f;
-    if (src < 0.f) src = 0.f;
-    i0 = (int)src;
-    if (i0 > in - 1) i0 = in - 1;
-    lam = fminf(fmaxf(src - (float)i0, 0.f), 1.f);
-    i1 = i0 + (i0 < in - 1 ? 1 : 0);
-}
-
-// The soft-argmax's shift.  Softmax is shift-invariant, so any shift that keeps the exponents non-positive and the sum z of the samples'
-// exponentials far from underflow gives the reference's value.  Pass 1 takes max(source): bilinear interpolation is a convex
-// combination, so it bounds the up-sampled maximum from ABOVE - but it is attained only where an output sample falls on the source
-// maximum.  An isolated peak between the samples of a 4x resize reaches weight 0.875^2 at best (largest exponent -0.234 (peak -
-// neighbours)), and a down-sampling grid can skip the source maximum altogether: for peaked logits every exponential underflows, z = 0
-// and sx / z is NaN.  With the TRUE up-sampled maximum as the shift the largest sample is exp(0), so z >= 1; with max(source) it is
-// z_true * exp(max(up) - max(source)).  z < READOUT_Z_MIN = 2^-64 therefore says that the bound overshot by more than 64 ln 2 = 44.4,
-// and the workgroup (z is block-uniform) takes the rare path: one walk for the exact max(lerp2) over the H x W samples, then pass 2
-// again with it.  While z >= 2^-64 the largest sample is >= 2^-64 / (H W) >= 2^-94 for H W <= 2^30, and every sample a float sum can still
-// see beside it (>= 2^-24 of it, i.e. >= 2^-118) is a normal float above 2^-126: nothing that matters was flushed or denormal, and the
-// common path's result stands as it was, bit for bit.  The exact maximum is a max over the same lerp2 values in both kernels (order
-// does not matter to a max), so the two forms agree bit for bit on the rare path as well.
-constexpr float READOUT_Z_MIN = 0x1p-64f;
-
-// A thread owns output columns x = tid, tid + 256, ... and walks down the rows: its x source indices / weight stay in
-// registers and the row's y indices / weight are wave-uniform, so a sample is 4 LDS reads + 3 lerps (the flat-index form
-// recomputed two source indices and an integer division per sample and was VALU-bound: 242 us per clip).
-__global__ __launch_bounds__(256) void track_readout_kernel(const float* __restrict__ masks, float* __restrict__ traj,
-                                                            float* __restrict__ vis, float* __restrict__ depth, int T,
-                                                            int h, int w, int H, int W) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* lo = (float*)smem;  // [3][h*w]
-    __shared__ float red[4][8];
-    const int n = blockIdx.x / T, t = blockIdx.x % T, tid = threadIdx.x;
-    const int hw = h * w;
-    for (int i = tid; i < 3 * hw; i += 256) {
-        const int m = i / hw, r = i % hw;
-        lo[i] = masks[(((long long)n * 3 + m) * T + t) * hw + r];
-    }
-    __syncthreads();
-    auto lerp2 = [&](const float* b, int r0, int r1, int x0, int x1, float lx, float ly) -> float {
-        const float top = (1.f - lx) * b[r0 + x0] + lx * b[r0 + x1];
-        const float bot = (1.f - lx) * b[r1 + x0] + lx * b[r1 + x1];
-        return (1.f - ly) * top + ly * bot;
-    };
-    // pass 1: an upper bound of channel 0 (max(source) >= the up-sampled maximum; not tight, see READOUT_Z_MIN) and the spatial sums of
-    // the up-sampled channels 1 and 2, all from the 64 x 64 source.  The sum of an up-sampled channel is
-    // sum_r b[r] * wy[row(r)] * wx[col(r)] with wx[i] / wy[i] = the total weight source column / row i receives from the W / H
-    // output positions (accumulated per source index in a fixed order).  Replaces a second walk over all H x W samples of
-    // three channels (12 LDS reads + 9 lerps per sample): 171 -> ~90 us per 64-track window.
-    float* wxs = lo + 3 * hw;  // [w]
-    float* wys = wxs + w;      // [h]
-    for (int i = tid; i < w + h; i += 256) {
-        const bool isx = i < w;
-        const int idx = isx ? i : i - w, in = isx ? w : h, out = isx ? W : H;
-        float acc = 0.f;
-        for (int d = 0; d < out; ++d) {
-            int i0, i1;
-            float lam;
-            src_idx_nc(d, in, out, i0, i1, lam);
-            if (i0 == idx) acc += 1.f - lam;
-            if (i1 == idx) acc += lam;
-        }
-        (isx ? wxs : wys)[idx] = acc;
-    }
-    __syncthreads();
-    float mx = -INFINITY, s1 = 0.f, s2 = 0.f;
-    for (int r = tid; r < hw; r += 256) {
-        const float wgt = wys[r / w] * wxs[r % w];
-        mx = fmaxf(mx, lo[r]);
-        s1 += lo[hw + r] * wgt;
-        s2 += lo[2 * hw + r] * wgt;
-    }
-    mx = wave_max(mx);
-    s1 = wave_sum(s1);
-    s2 = wave_sum(s2);
-    if ((tid & 63) == 0) {
-        red[tid >> 6][0] = mx;
-        red[tid >> 6][1] = s1;
-        red[tid >> 6][2] = s2;
-    }
-    __syncthreads();
-    mx = fmaxf(fmaxf(red[0][0], red[1][0]), fmaxf(red[2][0], red[3][0]));
-    s1 = red[0][1] + red[1][1] + red[2][1] + red[3][1];
-    s2 = red[0][2] + red[1][2] + red[2][2] + red[3][2];
-    __syncthreads();
-    // pass 2: soft-argmax (a second time with the exact maximum when the first sum says that max(source) overshot: READOUT_Z_MIN)
-    float z, sx, sy;
-    for (int exact = 0;; ++exact) {
-        z = 0.f, sx = 0.f, sy = 0.f;
-        for (int x = tid; x < W; x += 256) {
-            int x0, x1;
-            float lx;
-            src_idx_nc(x, w, W, x0, x1, lx);
-            const float xc = (float)x + 0.5f;
-#pragma unroll 2  // (two independent expf chains per trip, the sums in row order as before)
-            for (int y = 0; y < H; ++y) {
-                int y0, y1;
-                float ly;
-                src_idx_nc(y, h, H, y0, y1, ly);
-                // (expf, not v_exp_f32: the bare instruction is 13 us per launch faster, but its last-ulp differences moved one
-                //  re-seeded query of the 4-window full-size bf16 run onto another frame - the track then differs by 7e-2 in depth)
-                const float e = expf(lerp2(lo, y0 * w, y1 * w, x0, x1, lx, ly) - mx);
-                z += e;
-                sx += e * xc;
-                sy += e * ((float)y + 0.5f);
-            }
-        }
-        z = wave_sum(z);
-        sx = wave_sum(sx);
-        sy = wave_sum(sy);
-        if ((tid & 63) == 0) {
-            red[tid >> 6][0] = z;
-            red[tid >> 6][1] = sx;
-            red[tid >> 6][2] = sy;
-        }
-        __syncthreads();
-        z = red[0][0] + red[1][0] + red[2][0] + red[3][0];
-        sx = red[0][1] + red[1][1] + red[2][1] + red[3][1];
-        sy = red[0][2] + red[1][2] + red[2][2] + red[3][2];
-        if (exact || z >= READOUT_Z_MIN) break;  // block-uniform: every thread has read the same four partial sums
-        __syncthreads();
-        float m2 = -INFINITY;
-        for (int x = tid; x < W; x += 256) {
-            int x0, x1;
-            float lx;
-            src_idx_nc(x, w, W, x0, x1, lx);
-            for (int y = 0; y < H; ++y) {
-                int y0, y1;
-                float ly;
-                src_idx_nc(y, h, H, y0, y1, ly);
-                m2 = fmaxf(m2, lerp2(lo, y0 * w, y1 * w, x0, x1, lx, ly));
-            }
-        }
-        m2 = wave_max(m2);
-        if ((tid & 63) == 0) red[tid >> 6][0] = m2;
-        __syncthreads();
-        mx = fmaxf(fmaxf(red[0][0], red[1][0]), fmaxf(red[2][0], red[3][0]));
-        __syncthreads();
-    }
-    if (tid == 0) {
-        traj[((long long)n * 2 + 0) * T + t] = sx / z;
-        traj[((long long)n * 2 + 1) * T + t] = sy / z;
-        vis[(long long)n * T + t] = s1 / (float)(H * W);
-        depth[(long long)n * T + t] = expf(s2 / (float)(H * W));
-    }
-}
-
-// The same read-out on a 1024-thread workgroup (W <= 256; knob "readout_wide").  In the kernel above a thread owns an output column and
-// walks its H rows: H x (bilinear sample + expf) serially per thread on 224 of 256 threads - 58 us per launch whatever the number of
-// tracks, one launch per window.  Here the samples exp(logit - max) of RB rows at a time are formed by ALL threads into LDS, and the
-// column threads then add them up in the SAME order (row after row: z, sum e x, sum e y per column, then the wave / workgroup sums of
-// the kernel above): the same values in the same sums, bit for bit.
-constexpr int READOUT_RB = 32;
-__global__ __launch_bounds__(1024) void track_readout_wide_kernel(const float* __restrict__ masks, float* __restrict__ traj,
-                                                                  float* __restrict__ vis, float* __restrict__ depth, int T,
-                                                                  int h, int w, int H, int W) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* lo = (float*)smem;  // [3][h*w]
-    __shared__ float red[4][8];
-    const int n = blockIdx.x / T, t = blockIdx.x % T, tid = threadIdx.x;
-    const int hw = h * w;
-    float* wxs = lo + 3 * hw;        // [w]
-    float* wys = wxs + w;            // [h]
-    float* tlx = wys + h;            // [W] x interpolation weight
-    float* tly = tlx + W;            // [H]
-    int* tx0 = (int*)(tly + H);      // [W] x0 | x1 << 16
-    int* ty0 = tx0 + W;              // [H] y0 * w | (y1 * w) << 16
-    float* eb = (float*)(ty0 + H);   // [RB][W]
-    for (int i = tid; i < 3 * hw; i += 1024) {
-        const int m = i / hw, r = i % hw;
-        lo[i] = masks[(((long long)n * 3 + m) * T + t) * hw + r];
-    }
-    for (int i = tid; i < W + H; i += 1024) {
-        const bool isx = i < W;
-        const int d = isx ? i : i - W;
-        int i0, i1;
-        float lam;
-        src_idx_nc(d, isx ? w : h, isx ? W : H, i0, i1, lam);
-        if (isx) {
-            tlx[d] = lam;
-            tx0[d] = i0 | (i1 << 16);
-        } else {
-            tly[d] = lam;
-            ty0[d] = (i0 * w) | ((i1 * w) << 16);
-        }
-    }
-    __syncthreads();
-    auto lerp2 = [&](const float* b, int r0, int r1, int x0, int x1, float lx, float ly) -> float {
-        const float top = (1.f - lx) * b[r0 + x0] + lx * b[r0 + x1];
-        const float bot = (1.f - lx) * b[r1 + x0] + lx * b[r1 + x1];
-        return (1.f - ly) * top + ly * bot;
-    };
-    for (int i = tid; i < w + h; i += 1024) {
-        const bool isx = i < w;
-        const int idx = isx ? i : i - w, in = isx ? w : h, out = isx ? W : H;
-        float acc = 0.f;
-        for (int d = 0; d < out; ++d) {
-            int i0, i1;
-            float lam;
-            src_idx_nc(d, in, out, i0, i1, lam);
-            if (i0 == idx) acc += 1.f - lam;
-            if (i1 == idx) acc += lam;
-        }
-        (isx ? wxs : wys)[idx] = acc;
-    }
-    __syncthreads();
-    float mx = -INFINITY, s1 = 0.f, s2 = 0.f;
-    if (tid < 256) {  // (the partial sums of the 256-thread kernel: thread tid takes r = tid, tid + 256, ...)
-        for (int r = tid; r < hw; r += 256) {
-            const float wgt = wys[r / w] * wxs[r % w];
-            mx = fmaxf(mx, lo[r]);
-            s1 += lo[hw + r] * wgt;
-            s2 += lo[2 * hw + r] * wgt;
-        }
-        mx = wave_max(mx);
-        s1 = wave_sum(s1);
-        s2 = wave_sum(s2);
-        if ((tid & 63) == 0) {
-            red[tid >> 6][0] = mx;
-            red[tid >> 6][1] = s1;
-            red[tid >> 6][2] = s2;
-        }
-    }
-    __syncthreads();
-    mx = fmaxf(fmaxf(red[0][0], red[1][0]), fmaxf(red[2][0], red[3][0]));
-    s1 = red[0][1] + red[1][1] + red[2][1] + red[3][1];
-    s2 = red[0][2] + red[1][2] + red[2][2] + red[3][2];
-    __syncthreads();
-    // pass 2: soft-argmax (a second time with the exact maximum when the first sum says that max(source) overshot: READOUT_Z_MIN)
-    float z, sx, sy;
-    const float xc = (float)tid + 0.5f;
-    for (int exact = 0;; ++exact) {
-        z = 0.f, sx = 0.f, sy = 0.f;
-        for (int yb = 0; yb < H; yb += READOUT_RB) {
-            const int rows = H - yb < READOUT_RB ? H - yb : READOUT_RB;
-            for (int i = tid; i < rows * W; i += 1024) {
-                const int yy = i / W, x = i - yy * W;
-                const int px = tx0[x], py = ty0[yb + yy];
-                eb[i] = expf(lerp2(lo, py & 0xFFFF, py >> 16, px & 0xFFFF, px >> 16, tlx[x], tly[yb + yy]) - mx);
-            }
-            __syncthreads();
-            if (tid < W) {
-#pragma unroll 8  // (eight LDS reads in flight per trip, the sums in row order as before)
-                for (int yy = 0; yy < rows; ++yy) {
-                    const float e = eb[yy * W + tid];
-                    z += e;
-                    sx += e * xc;
-                    sy += e * ((float)(yb + yy) + 0.5f);
-                }
-            }
-            __syncthreads();
-        }
-        if (tid < 256) {
-            z = wave_sum(z);
-            sx = wave_sum(sx);
-            sy = wave_sum(sy);
-            if ((tid & 63) == 0) {
-                red[tid >> 6][0] = z;
-                red[tid >> 6][1] = sx;
-                red[tid >> 6][2] = sy;
-            }
-        }
-        __syncthreads();
-        z = red[0][0] + red[1][0] + red[2][0] + red[3][0];
-        sx = red[0][1] + red[1][1] + red[2][1] + red[3][1];
-        sy = red[0][2] + red[1][2] + red[2][2] + red[3][2];
-        if (exact || z >= READOUT_Z_MIN) break;  // block-uniform: every thread has read the same four partial sums
-        __syncthreads();
-        float m2 = -INFINITY;
-        for (int i = tid; i < H * W; i += 1024) {
-            const int y = i / W, x = i - y * W;
-            const int px = tx0[x], py = ty0[y];
-            m2 = fmaxf(m2, lerp2(lo, py & 0xFFFF, py >> 16, px & 0xFFFF, px >> 16, tlx[x], tly[y]));
-        }
-        m2 = wave_max(m2);
-        float* redw = &red[0][0];  // 16 waves: one float each of the 32
-        if ((tid & 63) == 0) redw[tid >> 6] = m2;
-        __syncthreads();
-        mx = -INFINITY;
-        for (int i = 0; i < 16; ++i) mx = fmaxf(mx, redw[i]);
-        __syncthreads();
-    }
-    if (tid == 0) {
-        traj[((long long)n * 2 + 0) * T + t] = sx / z;
-        traj[((long long)n * 2 + 1) * T + t] = sy / z;
-        vis[(long long)n * T + t] = s1 / (float)(H * W);
-        depth[(long long)n * T + t] = expf(s2 / (float)(H * W));
-    }
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -990,7 +640,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void i2t_delta_kernel(const T* __restrict__ probs, const T* __restrict__ vt,
                                                         const float* __restrict__ bias, T* __restrict__ delta, int P, int C,
                                                         int rows_per_wg) {
-    constexpr int K = 64, CW = 128;
+    constexpr int K = 64, CW = I2T_DELTA_CW;
     __shared__ __attribute__((aligned(16))) T tile[4][16 * CW];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, g = lane >> 4, i16 = lane & 15;
     const int c0 = blockIdx.x * CW, n = blockIdx.y, r0 = blockIdx.z * rows_per_wg;
@@ -1055,11 +705,11 @@ __global__ __launch_bounds__(256) void i2t_delta_kernel(const T* __restrict__ pr
 //   t2i_ctx:   ctx[(h * Rg + n * tokens + t)][c] = sum_splits scale * sum_{p in split} e[n][p][t * heads + h] * keys[n][p][c]
 //              (rows grouped by head, Rg rows per group: the A operand of the row-grouped-weights GEMM against Wv's head blocks)
 // ------------------------------------------------------------------------------------------------
-constexpr int T2I_SPLIT = 256;  // keys per softmax split
+// (T2I_SPLIT = 256 keys per softmax split, T2I_HT = 48: track_select.hpp)
 template <typename T>
 __global__ __launch_bounds__(192) void t2i_probs_kernel(const float* __restrict__ s, long long ld, T* __restrict__ probs,
                                                         float* __restrict__ stats, int P) {
-    constexpr int HT = 48, NCG = 12, NRL = 16, NR = T2I_SPLIT / NRL;
+    constexpr int HT = T2I_HT, NCG = 12, NRL = 16, NR = T2I_SPLIT / NRL;
     __shared__ __attribute__((aligned(16))) float red[NRL * HT];
     __shared__ __attribute__((aligned(16))) float stat[HT];
     const int sp_ = blockIdx.x, n = blockIdx.y, tid = threadIdx.x, cg = tid % NCG, rl = tid / NCG;
@@ -1116,9 +766,9 @@ __global__ __launch_bounds__(192) void t2i_probs_kernel(const float* __restrict_
     }
 }
 // scale[split][column] = exp(m_split - M) / Z from the splits' statistics of track n (M: the column maximum over all splits,
-// Z = sum_splits z_split exp(m_split - M)); nsp <= 16
+// Z = sum_splits z_split exp(m_split - M)); nsp <= T2I_MAX_SPLITS = 16
 __device__ __forceinline__ void t2i_scales(const float* __restrict__ stats, int n, int nsp, float* scale /* LDS [16][48] */) {
-    constexpr int HT = 48;
+    constexpr int HT = T2I_HT;
     const int tid = threadIdx.x;
     if (tid < HT) {
         const float* st = stats + (long long)n * nsp * 2 * HT;
@@ -1157,11 +807,12 @@ template <typename T, int HT, int CW, int ST = 4, int UNR = 1>
 __global__ __launch_bounds__(256) void t2i_ctx_mfma_kernel(const T* __restrict__ probs, const T* __restrict__ keys,
                                                            T* __restrict__ ctx, const float* __restrict__ stats, int P, int C, int heads,
                                                            int tokens, long long Rg, int shared_from) {
-    static_assert(HT == 48, "t2i_scales");
+    static_assert(HT == T2I_HT, "t2i_scales");
     static_assert(ST == 4 || ST == 8 || ST == 12, "ring depth");
-    constexpr int KT = 32, MT = HT / 16, NTW = CW / 64;  // NTW: 16-column tiles per wave
+    constexpr int KT = T2I_CTX_KT, MT = HT / 16, NTW = CW / 64;  // NTW: 16-column tiles per wave
     constexpr int SPK = T2I_SPLIT / KT;                          // key steps per softmax split
     constexpr int KB = KT * CW * 2, PB = KT * HT * 2, SB = KB + PB;
+    static_assert(SB == t2i_ctx_stage_bytes(CW), "the launcher's LDS size: ST stages");
     constexpr int KP = KB / 4096;  // 1 KB pieces of the key stage per wave
     constexpr int PW = PB / 1024;  // waves that carry a 1 KB piece of the probs stage (the others repeat the last piece)
     constexpr int CPR = CW / 8;    // 16-byte chunks per key row
@@ -1169,7 +820,7 @@ __global__ __launch_bounds__(256) void t2i_ctx_mfma_kernel(const T* __restrict__
     typedef __attribute__((address_space(3))) void* lptr_t;
     typedef const __attribute__((address_space(1))) void* gptr_t;
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    __shared__ float scale[16 * HT];
+    __shared__ float scale[T2I_MAX_SPLITS * HT];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int c0 = blockIdx.x * CW, n = blockIdx.y;
     const char* kb_own = (const char*)(keys + (long long)n * P * C + c0);
@@ -1285,7 +936,7 @@ template <typename T, int HT>
 __global__ __launch_bounds__(256) void t2i_ctx_kernel(const T* __restrict__ probs, const T* __restrict__ keys, T* __restrict__ ctx,
                                                       const float* __restrict__ stats, int P, int C, int heads, int tokens, long long Rg,
                                                       int shared_from) {
-    __shared__ float scale[16 * HT];
+    __shared__ float scale[T2I_MAX_SPLITS * HT];
     const int c = blockIdx.x * 256 + threadIdx.x, n = blockIdx.y;
     t2i_scales(stats, n, (P + T2I_SPLIT - 1) / T2I_SPLIT, scale);
     if (c >= C) return;
@@ -1317,22 +968,18 @@ __global__ __launch_bounds__(256) void t2i_ctx_kernel(const T* __restrict__ prob
 // ------------------------------------------------------------------------------------------------
 // launchers
 // ------------------------------------------------------------------------------------------------
-#define GRID1D(total, cap) ((int)(((total) + 255) / 256 < (cap) ? ((total) + 255) / 256 : (cap)))
+// Every launcher that chooses anything: its *_select (track_select.hpp) decides, the refusal leaves with the selection's text, and one
+// switch launches the form it names with the selection's grid, block and LDS size.
 
-// t2i_attn_kernel<T> with its LDS size: score rows [6][P], the queries [6][96] and 256 floats of scratch; the P.V partial sums
-// [nkg][6][hd] reuse the score rows, and the allocation grows by what they need beyond them (short P)
+// the SMALL_ATTN_T2I form (c: small_attn_select or t2i_attn_scores_select); pre: scores formed elsewhere, or null
 template <typename T>
-static int launch_t2i_attn(const void* q, const void* k, const void* v, void* out, int N, int P, int D, int heads, int hd, float scale,
-                           long long kv_stride, const float* pre, long long ld_pre, int pre_heads, hipStream_t stream) {
-    const int ncg = hd / 4, nkg = 256 / ncg;
-    size_t lds = (size_t)(6 * P + 6 * 96 + 256) * 4;
-    const size_t need2 = (size_t)nkg * 6 * hd * 4;
-    if (need2 > (size_t)6 * P * 4) lds += need2 - (size_t)6 * P * 4;
+static int launch_t2i_attn(const SmallAttnChoice& c, const void* q, const void* k, const void* v, void* out, int P, int D, const float* pre,
+                           long long ld_pre, int pre_heads, hipStream_t stream) {
     auto kern = t2i_attn_kernel<T>;
     static lds_attr_state attr_done;
-    HIP_TRY(lds_attr_once(attr_done, kern, (int)lds));
-    hipLaunchKernelGGL(kern, dim3(N, heads), dim3(256), lds, stream, (const T*)q, (const T*)k, (const T*)v, (T*)out, P, D, hd, scale,
-                       kv_stride, pre, ld_pre, pre_heads);
+    HIP_TRY(lds_attr_once(attr_done, kern, (int)c.lds_bytes));
+    hipLaunchKernelGGL(kern, grid_of(c), dim3(c.block), c.lds_bytes, stream, (const T*)q, (const T*)k, (const T*)v, (T*)out, P, D, c.hd, c.scale,
+                       c.stride, pre, ld_pre, pre_heads);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1340,24 +987,20 @@ static int launch_t2i_attn(const void* q, const void* k, const void* v, void* ou
 // tokens -> image attention from scores formed elsewhere (folded keys): softmax over the P keys per (track, token, head), then P.V
 int launch_t2i_attn_scores(int dtype, const float* scores, long long ld_scores, const void* v, void* out, int N, int P, int D, int heads,
                            hipStream_t stream) {
-    const int hd = heads > 0 ? D / heads : 0;
-    if (heads < 1 || hd * heads != D || hd % 4 || hd > 96 || P % 4 || ld_scores < 6 * heads) {
-        l4p_set_error("t2i_attn_scores: D = heads * hd with hd %% 4 == 0, hd <= 96, P %% 4 == 0, ld_scores >= 6 * heads");
-        return L4P_E_INVALID;
-    }
-    ProfScope prof(PROF_TRACK, stream, "small_attn kind5 N%d P%d D%d", N, P, D);
-    L4P_WITH_T(dtype, T, return launch_t2i_attn<T>(nullptr, nullptr, v, out, N, P, D, heads, hd, 1.f, (long long)P * D, scores, ld_scores, heads, stream));
+    const char* err = "";
+    const SmallAttnChoice c = t2i_attn_scores_select(N, P, D, heads, ld_scores, &err);
+    if (track_refused(c)) return l4p_refuse(err, "t2i_attn_scores", P, c.hd, c.lds_bytes, LDS_DEVICE_LIMIT);  // (the argument refusal's text takes none)
+    ProfScope prof(PROF_TRACK, stream, small_attn_form_tag(), 5, N, P, D);
+    L4P_WITH_T(dtype, T, return launch_t2i_attn<T>(c, nullptr, nullptr, v, out, P, D, scores, ld_scores, heads, stream));
 }
 int launch_i2t_probs(int dtype, const float* s, long long lds_, int pairs, const float* cbias, int rows_per_group, void* p, int ldp,
                      long long M, int heads, int tokens, hipStream_t stream) {
-    if (tokens < 1 || tokens > 8 || heads < 1 || ldp < tokens * heads || lds_ < (pairs ? 2 : 1) * tokens * heads || (cbias && rows_per_group < 1)) {
-        l4p_set_error("i2t_probs: 1 <= tokens <= 8, ldp >= tokens * heads, score row stride >= (pairs ? 2 : 1) * tokens * heads");
-        return L4P_E_INVALID;
-    }
-    ProfScope prof(PROF_TRACK, stream, "i2t_probs");
-    const int grid = GRID1D(M * heads, 16384);
-    L4P_WITH_T(dtype, T, hipLaunchKernelGGL(i2t_probs_kernel<T>, dim3(grid), dim3(256), 0, stream, s, lds_, pairs, cbias, rows_per_group, (T*)p, ldp, M,
-                                            heads, tokens));
+    const char* err = "";
+    const TrackChoice c = i2t_probs_select(M, heads, tokens, ldp, lds_, pairs, cbias != nullptr, rows_per_group, &err);
+    if (track_refused(c)) return l4p_refuse(err);
+    ProfScope prof(PROF_TRACK, stream, "%s", i2t_probs_form_tag());
+    L4P_WITH_T(dtype, T, hipLaunchKernelGGL(i2t_probs_kernel<T>, grid_of(c), dim3(c.block), 0, stream, s, lds_, pairs, cbias, rows_per_group, (T*)p,
+                                            ldp, M, heads, tokens));
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1367,7 +1010,7 @@ int launch_split_hilo(int dtype, const float* in, void* out, int G, int R, long 
         return L4P_E_INVALID;
     }
     ProfScope prof(PROF_TRACK, stream, "split_hilo");
-    const int grid = GRID1D((long long)G * R * C, 16384);
+    const int grid = grid1d((long long)G * R * C, 16384);
     L4P_WITH_T(dtype, T, hipLaunchKernelGGL(split_hilo_kernel<T>, dim3(grid), dim3(256), 0, stream, in, (T*)out, G, R, C));
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1378,7 +1021,7 @@ int launch_transpose_pad(int dtype, const void* in, void* out, int G, int R, int
         return L4P_E_INVALID;
     }
     ProfScope prof(PROF_TRACK, stream, "transpose_pad");
-    const int grid = GRID1D((long long)G * C * Rp, 16384);
+    const int grid = grid1d((long long)G * C * Rp, 16384);
     L4P_WITH_T(dtype, T, hipLaunchKernelGGL(transpose_pad_kernel<T>, dim3(grid), dim3(256), 0, stream, (const T*)in, (T*)out, G, R, C, Rp));
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1386,69 +1029,61 @@ int launch_transpose_pad(int dtype, const void* in, void* out, int G, int R, int
 
 int launch_i2t_delta(int dtype, const void* probs, const void* vt, const float* bias, void* delta, int N, int P, int C, int K,
                      hipStream_t stream) {
-    if (!is16(dtype) || K != 64 || C % 128 || P % 16 || N < 1) {
-        l4p_set_error("i2t_delta: 16-bit engine, k = 64, C %% 128 == 0, P %% 16 == 0 (other shapes: the row-grouped-weights GEMM)");
-        return L4P_E_INVALID;
-    }
+    const char* err = "";
+    const TrackChoice c = i2t_delta_select(dtype, N, P, C, K, &err);
+    if (track_refused(c)) return l4p_refuse(err);
     // (a batched GEMM - profiled with the small / streaming products under the tag of the launch it replaces: the executed-shapes check sees it)
-    ProfScope prof(PROF_GEMM_SMALL, stream, "M%lld N%d K%d epi0 act0 delta t16x128 wgrp", (long long)N * P, C, K);
-    const int rs = P % 128 == 0 ? 2 : 1;
-    L4P_WITH_T16(dtype, T16, hipLaunchKernelGGL(i2t_delta_kernel<T16>, dim3(C / 128, N, rs), dim3(256), 0, stream, (const T16*)probs, (const T16*)vt, bias,
-                       (T16*)delta, P, C, P / rs));
+    ProfScope prof(PROF_GEMM_SMALL, stream, i2t_delta_form_tag(), (long long)N * P, C, K);
+    L4P_WITH_T16(dtype, T16, hipLaunchKernelGGL(i2t_delta_kernel<T16>, grid_of(c), dim3(c.block), 0, stream, (const T16*)probs, (const T16*)vt, bias,
+                       (T16*)delta, P, C, P / c.gz));
     HIP_TRY(hipGetLastError());
     return 0;
 }
 int launch_t2i_probs(int dtype, const float* scores, long long ld_scores, void* probs, float* stats, int N, int P, int HT, hipStream_t stream) {
-    if (N < 1 || P < 1 || P > 16 * T2I_SPLIT || HT != 48 || ld_scores < HT || ld_scores % 4) {
-        l4p_set_error("t2i_probs: HT == 48, P <= 4096, score row stride >= HT and a multiple of 4");
-        return L4P_E_INVALID;
-    }
-    ProfScope prof(PROF_TRACK, stream, "t2i_probs");
-    const dim3 grid((P + T2I_SPLIT - 1) / T2I_SPLIT, N);
-    L4P_WITH_T(dtype, T, hipLaunchKernelGGL(t2i_probs_kernel<T>, grid, dim3(192), 0, stream, scores, ld_scores, (T*)probs, stats, P));
+    const char* err = "";
+    const TrackChoice c = t2i_probs_select(N, P, HT, ld_scores, &err);
+    if (track_refused(c)) return l4p_refuse(err);
+    ProfScope prof(PROF_TRACK, stream, "%s", t2i_probs_form_tag());
+    L4P_WITH_T(dtype, T, hipLaunchKernelGGL(t2i_probs_kernel<T>, grid_of(c), dim3(c.block), 0, stream, scores, ld_scores, (T*)probs, stats, P));
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+// one instantiation of the MFMA context kernel: a ring of ST stages, UNR of them consumed per barrier
+template <typename T16, int CW, int ST, int UNR>
+static int launch_t2i_ctx_mfma(const T2iContextChoice& c, const void* probs, const float* stats, const void* keys, void* ctx, int P, int C, int heads,
+                               int tokens, long long Rg, hipStream_t stream) {
+    constexpr int lds = ST * t2i_ctx_stage_bytes(CW);  // (= c.lds_bytes: the selection sizes the form's ring by the same two functions)
+    auto kern = t2i_ctx_mfma_kernel<T16, T2I_HT, CW, ST, UNR>;
+    static lds_attr_state attr_done;
+    HIP_TRY(lds_attr_once(attr_done, kern, lds));
+    hipLaunchKernelGGL(kern, grid_of(c), dim3(c.block), lds, stream, (const T16*)probs, (const T16*)keys, (T16*)ctx, stats, P, C, heads, tokens, Rg,
+                       c.shared_from);
     return 0;
 }
 int launch_t2i_context(int dtype, const void* probs, const float* stats, const void* keys, void* ctx, int N, int P, int C, int heads,
                        int tokens, long long Rg, int shared_from, hipStream_t stream) {
-    if (N < 1 || heads * tokens != 48 || C % 64 || P % 32 || P < 96 || P > 16 * T2I_SPLIT || Rg < (long long)N * tokens || shared_from < 0 ||
-        shared_from % 32) {
-        l4p_set_error("t2i_context: heads * tokens == 48, C %% 64 == 0, P %% 32 == 0, 96 <= P <= 4096, Rg >= N * tokens, shared_from %% 32 == 0");
-        return L4P_E_INVALID;
-    }
-    if (shared_from > P) shared_from = P;
+    const TrackKnobs knobs = {knob(KNOB_TRACK_DEEP), knob(KNOB_READOUT_WIDE)};
+    const char* err = "";
+    const T2iContextChoice c = t2i_context_select(dtype, N, P, C, heads, tokens, Rg, shared_from, knobs, &err);
+    if (track_refused(c)) return l4p_refuse(err);
     // (a batched GEMM: N x [HT x P] x [P x C]; profiled with the small / streaming products: the FLOP model's executed-shapes check sees it)
-    ProfScope prof(PROF_GEMM_SMALL, stream, "M%d N%d K%d epi0 act0 ctx t48x%d", N * heads * tokens, C, P, C % 128 ? 64 : 128);
-    if (is16(dtype)) L4P_WITH_T16(dtype, T16, {
-        // at most one workgroup per CU (a rank's query shard): four 32-key stages per barrier on a twelve-stage ring (8 tracks: 53.8 -> 34.2 us;
-        // two per barrier: 39.0), else - P not a multiple of 128 - two
-        if (C % 128 == 0 && (C / 128) * N <= 256 && P % 128 == 0 && knob(KNOB_TRACK_DEEP)) {
-            constexpr int lds = 12 * (32 * 128 * 2 + 32 * 48 * 2);
-            auto kern = t2i_ctx_mfma_kernel<T16, 48, 128, 12, 4>;
-            static lds_attr_state attr_quads;
-            HIP_TRY(lds_attr_once(attr_quads, kern, lds));
-            hipLaunchKernelGGL(kern, dim3(C / 128, N), dim3(256), lds, stream, (const T16*)probs, (const T16*)keys, (T16*)ctx, stats, P, C,
-                               heads, tokens, Rg, shared_from);
-        } else if (C % 128 == 0 && (C / 128) * N <= 256 && P % 64 == 0 && knob(KNOB_TRACK_DEEP)) {
-            constexpr int lds = 8 * (32 * 128 * 2 + 32 * 48 * 2);
-            auto kern = t2i_ctx_mfma_kernel<T16, 48, 128, 8, 2>;
-            static lds_attr_state attr_pairs;
-            HIP_TRY(lds_attr_once(attr_pairs, kern, lds));
-            hipLaunchKernelGGL(kern, dim3(C / 128, N), dim3(256), lds, stream, (const T16*)probs, (const T16*)keys, (T16*)ctx, stats, P, C,
-                               heads, tokens, Rg, shared_from);
-        } else if (C % 128 == 0) {
-            constexpr int lds = 4 * (32 * 128 * 2 + 32 * 48 * 2);
-            hipLaunchKernelGGL((t2i_ctx_mfma_kernel<T16, 48, 128>), dim3(C / 128, N), dim3(256), lds, stream, (const T16*)probs,
-                               (const T16*)keys, (T16*)ctx, stats, P, C, heads, tokens, Rg, shared_from);
-        } else {
-            constexpr int lds = 4 * (32 * 64 * 2 + 32 * 48 * 2);
-            hipLaunchKernelGGL((t2i_ctx_mfma_kernel<T16, 48, 64>), dim3(C / 64, N), dim3(256), lds, stream, (const T16*)probs,
-                               (const T16*)keys, (T16*)ctx, stats, P, C, heads, tokens, Rg, shared_from);
-        }
-    }); else {
-        hipLaunchKernelGGL((t2i_ctx_kernel<float, 48>), dim3((C + 255) / 256, N), dim3(256), 0, stream, (const float*)probs,
-                           (const float*)keys, (float*)ctx, stats, P, C, heads, tokens, Rg, shared_from);
+    ProfScope prof(PROF_GEMM_SMALL, stream, t2i_context_form_tag(C), N * heads * tokens, C, P);
+    // (UNR: stages per barrier - a quarter of the ring of the deep forms)
+#define CTX_LAUNCH(FORM, UNR)                                                                                                            \
+    L4P_WITH_T16(dtype, T16, rc = (launch_t2i_ctx_mfma<T16, t2i_ctx_columns(FORM), t2i_ctx_ring(FORM), UNR>(c, probs, stats, keys, ctx, P, C, heads, \
+                                                                                                           tokens, Rg, stream)))
+    int rc = 0;
+    switch (c.form) {
+        case T2I_CTX_RING12: CTX_LAUNCH(T2I_CTX_RING12, 4); break;
+        case T2I_CTX_RING8: CTX_LAUNCH(T2I_CTX_RING8, 2); break;
+        case T2I_CTX_RING4: CTX_LAUNCH(T2I_CTX_RING4, 1); break;
+        case T2I_CTX_MFMA64: CTX_LAUNCH(T2I_CTX_MFMA64, 1); break;
+        default:  // T2I_CTX_F32
+            hipLaunchKernelGGL((t2i_ctx_kernel<float, T2I_HT>), grid_of(c), dim3(c.block), 0, stream, (const float*)probs, (const float*)keys,
+                               (float*)ctx, stats, P, C, heads, tokens, Rg, c.shared_from);
     }
+#undef CTX_LAUNCH
+    if (rc) return rc;
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1475,7 +1110,7 @@ int launch_track_keys_init(int dtype, const float* enc, const float* hist, const
     const long long shared8 = shared_from > 0 ? (long long)shared_from * C / 8 : per_q8;  // (0: no shared rows)
     if (shared_from == 0) k32_shared = nullptr;
     ProfScope prof(PROF_TRACK, stream, "track_keys_init");
-    L4P_WITH_T(dtype, T, hipLaunchKernelGGL(track_keys_init_kernel<T>, dim3(GRID1D(total8, 16384)), dim3(256), 0, stream, enc, hist, pos, k32,
+    L4P_WITH_T(dtype, T, hipLaunchKernelGGL(track_keys_init_kernel<T>, dim3(grid1d(total8, 16384)), dim3(256), 0, stream, enc, hist, pos, k32,
                                             (T*)kT, (T*)kP, per_q8, total8, shared8, k32_shared));
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1499,7 +1134,7 @@ int launch_broadcast_block(void* base, long long off, long long bytes, long long
     }
     if (n <= 1 || bytes == 0) return 0;
     ProfScope prof(PROF_TRACK, stream, "broadcast_block");
-    hipLaunchKernelGGL(broadcast_block_kernel, dim3(GRID1D(bytes / 16 * (n - 1), 16384)), dim3(256), 0, stream, (char*)base, off,
+    hipLaunchKernelGGL(broadcast_block_kernel, dim3(grid1d(bytes / 16 * (n - 1), 16384)), dim3(256), 0, stream, (char*)base, off,
                        bytes / 16, stride, n);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1508,7 +1143,7 @@ int launch_broadcast_block(void* base, long long off, long long bytes, long long
 int launch_fill_rows(float* out, const float* v, long long rows, int C, long long group_rows, long long group_stride,
                      long long group_off, hipStream_t stream) {
     ProfScope prof(PROF_TRACK, stream, "fill_rows");
-    hipLaunchKernelGGL(fill_rows_kernel, dim3(GRID1D(rows * (C / 4), 16384)), dim3(256), 0, stream, out, v, rows, C,
+    hipLaunchKernelGGL(fill_rows_kernel, dim3(grid1d(rows * (C / 4), 16384)), dim3(256), 0, stream, out, v, rows, C,
                        group_rows, group_stride, group_off);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -1516,180 +1151,30 @@ int launch_fill_rows(float* out, const float* v, long long rows, int C, long lon
 
 int launch_small_attn(int dtype, int kind, const void* q, const void* k, const void* v, void* out, int N, int P, int D,
                       int heads, hipStream_t stream) {
-    const int hd = D / heads;
-    const float scale = 1.0f / sqrtf((float)hd);
-    if (hd * heads != D || (kind != 0 && (hd % 4 || hd > 96)) || ((kind == 1 || kind == 3) && P % 4)) {  // (P % 4: 16-byte LDS rows)
-        l4p_set_error("small_attn: unsupported head geometry D=%d heads=%d", D, heads);
-        return L4P_E_INVALID;
-    }
-    ProfScope prof(PROF_TRACK, stream, "small_attn kind%d N%d P%d D%d", kind, N, P, D);
-    if (kind == 0) {  // 6 x 6 self attention
-        L4P_WITH_T(dtype, T, hipLaunchKernelGGL(self_attn6_kernel<T>, dim3(N, heads), dim3(64), 0, stream, (const T*)q, (const T*)k,
-                                                (const T*)v, (T*)out, D, hd, scale));
-    } else if (kind == 1 || kind == 3) {  // tokens -> image (3: one K / V set shared by every query)
-        const long long kv_stride = kind == 1 ? (long long)P * D : 0;
-        L4P_WITH_T(dtype, T, return launch_t2i_attn<T>(q, k, v, out, N, P, D, heads, hd, scale, kv_stride, nullptr, 0, 0, stream));
-    } else if (kind == 2 || kind == 4) {  // image -> tokens (4: one query set shared by every track)
-        const long long q_stride = kind == 2 ? (long long)P * D : 0;
-        if (256 % heads == 0 && (D * (esize_of(dtype))) % 16 == 0) {
-            const int rows = 256 / heads, es = esize_of(dtype);
-            const size_t lds = (((size_t)12 * D * 4 + 15) & ~(size_t)15) + (size_t)rows * D * es;
-            const dim3 grid((P + rows - 1) / rows, N);
+    const char* err = "";
+    const SmallAttnChoice c = small_attn_select(dtype, kind, N, P, D, heads, &err);
+    if (c.form == TRACK_FORM_INVALID) return l4p_refuse(err, D, heads);
+    if (c.form == TRACK_FORM_LDS_REFUSED) return l4p_refuse(err, "small_attn", P, c.hd, c.lds_bytes, LDS_DEVICE_LIMIT);
+    ProfScope prof(PROF_TRACK, stream, small_attn_form_tag(), kind, N, P, D);
+    switch (c.form) {
+        case SMALL_ATTN_SELF6:
+            L4P_WITH_T(dtype, T, hipLaunchKernelGGL(self_attn6_kernel<T>, grid_of(c), dim3(c.block), 0, stream, (const T*)q, (const T*)k, (const T*)v,
+                                                    (T*)out, D, c.hd, c.scale));
+            break;
+        case SMALL_ATTN_T2I: L4P_WITH_T(dtype, T, return launch_t2i_attn<T>(c, q, k, v, out, P, D, nullptr, 0, 0, stream));
+        case SMALL_ATTN_I2T_LDS:
+        case SMALL_ATTN_I2T:  // (the direct form raises its limit as well: past D = 1365 the key and value rows alone are over 64 KB)
             L4P_WITH_T(dtype, T, {
-                auto kern = i2t_attn_lds_kernel<T>;
-                static lds_attr_state attr_done;
-                HIP_TRY(lds_attr_once(attr_done, kern, (int)lds));
-                hipLaunchKernelGGL(kern, grid, dim3(256), lds, stream, (const T*)q, (const T*)k, (const T*)v, (T*)out, P, D, hd, heads,
-                                   scale, q_stride);
+                const bool staged = c.form == SMALL_ATTN_I2T_LDS;
+                auto kern = staged ? i2t_attn_lds_kernel<T> : i2t_attn_kernel<T>;
+                static lds_attr_state attr_staged, attr_direct;
+                HIP_TRY(lds_attr_once(staged ? attr_staged : attr_direct, kern, (int)c.lds_bytes));
+                hipLaunchKernelGGL(kern, grid_of(c), dim3(c.block), c.lds_bytes, stream, (const T*)q, (const T*)k, (const T*)v, (T*)out, P, D, c.hd,
+                                   heads, c.scale, c.stride);
             });
-            HIP_TRY(hipGetLastError());
-            return 0;
-        }
-        const size_t lds = (size_t)12 * D * 4;
-        const dim3 grid((P * heads + 255) / 256, N);
-        L4P_WITH_T(dtype, T, hipLaunchKernelGGL(i2t_attn_kernel<T>, grid, dim3(256), lds, stream, (const T*)q, (const T*)k, (const T*)v,
-                                                (T*)out, P, D, hd, heads, scale, q_stride));
+            break;
+        default: break;  // SMALL_ATTN_NONE
     }
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// LDS-staged form (VT threads, one voxel each; 45 KB of LDS at bf16, three workgroups per CU so one's copy overlaps
-// another's arithmetic): the workgroup copies VT voxels x Cc channels (one contiguous span of `up`) into LDS with coalesced
-// 16-byte LDS-DMA and each thread then walks its own voxel row from LDS.  The direct form above reads 16 bytes per lane at
-// a Cc*sizeof(T) stride (64 distinct lines per load instruction): 1.1 TB/s measured, this one streams.  Same summation order.
-template <typename T, int VT>
-__global__ __launch_bounds__(VT) void mask_product_lds_kernel(const T* __restrict__ up, const float* __restrict__ hyper,
-                                                               float* __restrict__ masks, long long vox, int Cc) {
-    typedef const __attribute__((address_space(1))) void* gptr_t;
-    typedef __attribute__((address_space(3))) void* lptr_t;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    float* hs = (float*)smem;                 // [3][Cc]
-    char* tile = smem + ((3 * Cc * 4 + 15) & ~15);  // [VT][Cc] T
-    const int n = blockIdx.y, tid = threadIdx.x;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const long long p0 = (long long)blockIdx.x * VT;
-    const int nvox = (int)(vox - p0 < VT ? vox - p0 : VT);
-    const int chunks = nvox * Cc * (int)sizeof(T) / 16;
-    const char* src = (const char*)(up + ((long long)n * vox + p0) * Cc);
-    for (int c = 0; c < chunks; c += VT)
-        if (c + tid < chunks)
-            __builtin_amdgcn_global_load_lds((gptr_t)(src + (long long)(c + tid) * 16), (lptr_t)(tile + (c + wave * 64) * 16), 16, 0, 0);
-    for (int i = tid; i < 3 * Cc; i += VT) hs[i] = hyper[(long long)n * 3 * Cc + i];
-    __syncthreads();
-    if (tid < nvox) {
-        const T* xp = (const T*)tile + (long long)tid * Cc;
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-        for (int c0 = 0; c0 < Cc; c0 += 8) {
-            float x[8];
-            Vec8<T>::load(xp + c0, x);
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                a0 += x[e] * hs[c0 + e];
-                a1 += x[e] * hs[Cc + c0 + e];
-                a2 += x[e] * hs[2 * Cc + c0 + e];
-            }
-        }
-        const long long p = p0 + tid;
-        masks[((long long)n * 3 + 0) * vox + p] = a0;
-        masks[((long long)n * 3 + 1) * vox + p] = a1;
-        masks[((long long)n * 3 + 2) * vox + p] = a2;
-    }
-}
-
-int launch_mask_product(int dtype, const void* up, const float* hyper, float* masks, int N, long long vox, int Cc,
-                        hipStream_t stream) {
-    if (Cc % 8) {
-        l4p_set_error("mask_product: C %% 8 != 0");
-        return L4P_E_INVALID;
-    }
-    ProfScope prof(PROF_TRACK, stream, "mask_product");
-    const int es = esize_of(dtype);
-    const int VT = 128;
-    const size_t lds_tile = ((size_t)3 * Cc * 4 + 15) / 16 * 16 + (size_t)VT * Cc * es;
-    if (lds_tile <= LDS_DEVICE_LIMIT) {
-        const dim3 grid((unsigned)((vox + VT - 1) / VT), N);
-        L4P_WITH_T(dtype, T, {
-            auto kern = mask_product_lds_kernel<T, 128>;
-            static lds_attr_state attr_done;
-            HIP_TRY(lds_attr_once(attr_done, kern, (int)lds_tile));
-            hipLaunchKernelGGL(kern, grid, dim3(128), lds_tile, stream, (const T*)up, hyper, masks, vox, Cc);
-        });
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
-    const dim3 grid(GRID1D(vox, 1024), N);
-    const size_t lds = (size_t)3 * Cc * 4;
-    L4P_WITH_T(dtype, T, hipLaunchKernelGGL(mask_product_kernel<T>, grid, dim3(256), lds, stream, (const T*)up, hyper, masks, vox, Cc));
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-// masks[n][i][t][y][x] = sum over the chunks of tap (y%2, x%2) of the L4P_EPI_MASKDOT partial sums [chunk][i][m] of row
-// m = ((n*T + t)*h + y/2)*w + x/2 (see include/l4p_hip.h).  One thread per output voxel, fixed summation order.
-__global__ void mask_gather_kernel(const float* __restrict__ partial, float* __restrict__ masks, int N, int T, int h, int w,
-                                   int cpt) {
-    const int H2 = 2 * h, W2 = 2 * w;
-    const long long vox = (long long)T * H2 * W2, total = vox * N, M = (long long)N * T * h * w;
-    for (long long i = blockIdx.x * (long long)blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
-        const int x = (int)(i % W2);
-        long long r = i / W2;
-        const int y = (int)(r % H2);
-        r /= H2;
-        const int t = (int)(r % T), n = (int)(r / T);
-        const long long m = (((long long)n * T + t) * h + (y >> 1)) * w + (x >> 1);
-        const int tap = (y & 1) * 2 + (x & 1);
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-        for (int c = 0; c < cpt; ++c) {
-            const float* pp = partial + (long long)(tap * cpt + c) * 3 * M + m;
-            a0 += pp[0];
-            a1 += pp[M];
-            a2 += pp[2 * M];
-        }
-        const long long p = ((long long)t * H2 + y) * W2 + x;
-        masks[((long long)n * 3 + 0) * vox + p] = a0;
-        masks[((long long)n * 3 + 1) * vox + p] = a1;
-        masks[((long long)n * 3 + 2) * vox + p] = a2;
-    }
-}
-
-int launch_mask_gather(const float* partial, float* masks, int N, int T, int h, int w, int cpt, hipStream_t stream) {
-    const long long total = (long long)N * T * 4 * h * w;
-    ProfScope prof(PROF_TRACK, stream, "mask_gather");
-    hipLaunchKernelGGL(mask_gather_kernel, dim3(GRID1D(total, 16384)), dim3(256), 0, stream, partial, masks, N, T, h, w, cpt);
-    HIP_TRY(hipGetLastError());
-    return 0;
-}
-
-int launch_track_readout(const float* masks, float* traj, float* vis, float* depth, int N, int T, int h, int w, int H,
-                         int W, hipStream_t stream) {
-    if (!masks || !traj || !vis || !depth || N < 1 || T < 1 || h < 1 || w < 1 || H < 1 || W < 1 || (long long)N * T > 0x7FFFFFFFLL) {
-        l4p_set_error("track_readout: needs every pointer and N, T, h, w, H, W >= 1 (N=%d T=%d h=%d w=%d H=%d W=%d)", N, T, h, w, H, W);
-        return L4P_E_INVALID;
-    }
-    // both kernels keep the three low-resolution maps in LDS (+ the 128 static bytes of red[][])
-    const size_t lds_static = 4 * 8 * sizeof(float);
-    const unsigned long long lds_need = (3ull * (unsigned long long)h * w + w + h) * 4 + lds_static;
-    if (lds_need > LDS_DEVICE_LIMIT) {
-        l4p_set_error("track_readout: the %d x %d source maps need %llu bytes of LDS, the device has %zu", h, w, lds_need, LDS_DEVICE_LIMIT);
-        return L4P_E_INVALID;
-    }
-    // the 1024-thread form: few (track, frame) workgroups - a rank's query shard of the sharded long video - leave most of the chip idle
-    // and the launch is one workgroup's serial walk; with many tracks the 256-thread form fills the chip just as well
-    const size_t lds_wide = ((size_t)3 * h * w + w + h + 2 * (W + H) + (size_t)READOUT_RB * W) * 4;
-    if (knob(KNOB_READOUT_WIDE) && W <= 256 && h * w < 65536 && N * T <= 512 && lds_wide + lds_static <= LDS_DEVICE_LIMIT) {
-        static lds_attr_state attr_wide;
-        HIP_TRY(lds_attr_once(attr_wide, track_readout_wide_kernel, (int)lds_wide));
-        ProfScope prof(PROF_TRACK, stream, "track_readout wide");
-        hipLaunchKernelGGL(track_readout_wide_kernel, dim3(N * T), dim3(1024), lds_wide, stream, masks, traj, vis, depth, T, h, w, H, W);
-        HIP_TRY(hipGetLastError());
-        return 0;
-    }
-    const size_t lds = ((size_t)3 * h * w + w + h) * 4;
-    static lds_attr_state attr_done;
-    HIP_TRY(lds_attr_once(attr_done, track_readout_kernel, (int)lds));
-    ProfScope prof(PROF_TRACK, stream, "track_readout");
-    hipLaunchKernelGGL(track_readout_kernel, dim3(N * T), dim3(256), lds, stream, masks, traj, vis, depth, T, h, w, H, W);
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -1711,7 +1196,7 @@ int launch_track_commit(const float* w_traj, const float* w_vis, const float* w_
     hipLaunchKernelGGL(track_commit_kernel, dim3((N + 63) / 64), dim3(64), 0, stream, w_traj, w_vis, w_depth, valid_t,
                        valid_n, traj, vis, depth, T, start, ws, next_start, last_window, cur_q, plabel, best_out, N);
     if (!last_window && new_pfeat && pfeat)
-        hipLaunchKernelGGL(masked_rows_copy_kernel, dim3(GRID1D((long long)N * (C / 4), 4096)), dim3(256), 0, stream, pfeat,
+        hipLaunchKernelGGL(masked_rows_copy_kernel, dim3(grid1d((long long)N * (C / 4), 4096)), dim3(256), 0, stream, pfeat,
                            new_pfeat, valid_n, N, C);
     HIP_TRY(hipGetLastError());
     return 0;

@@ -28,7 +28,8 @@ UPSAMPLE_CASES = [
     ("c352_div", 1, (2, 6, 5), (3, 12, 11), 352, True),              # C / 8 = 44: the division path at the DPT fusion width
 ]
 
-# (N, P, D, heads) of l4p_small_attn kinds 1 - 4 and l4p_t2i_attn_scores (hd = D / heads <= 96)
+# (N, P, D, heads) of l4p_small_attn kinds 1 - 4 and l4p_t2i_attn_scores (hd = D / heads <= 96).  The comments say what each shape is
+# for; that it reaches the kernel form named (i2t LDS / direct), with which grid and LDS size, is asserted by tests/test_track_select_cpu.py
 ATTN_SHAPES = [
     (3, 2048, 704, 8),   # the full model's shape: hd 88, whole-row score form (16-bit), i2t LDS kernel with 32 rows
     (2, 96, 352, 4),     # P < 256 (tid < P on the first row load); P < 1024: grown LDS of the P.V reduction; i2t rows = 64, ragged
@@ -158,7 +159,8 @@ def mask_product_ref(up, hyper):
 # tracker output tail: gather of the mask up-scaling's partial sums, read-out of the mask logits
 # ------------------------------------------------------------------------------------------------
 # id, (N, T), (h, w), (H, W), wide: whether launch_track_readout takes the 1024-thread form with the knob readout_wide on
-# (W <= 256, N T <= 512 and its LDS request (3 h w + w + h + 2 (W + H) + 32 W) * 4 <= 160 KiB)
+# (W <= 256, N T <= 512 and its LDS request (3 h w + w + h + 2 (W + H) + 32 W) * 4 <= 160 KiB).  The flag restates the rule by hand:
+# tests/test_track_select_cpu.py holds it to the selection itself (csrc/track_select.hpp track_readout_select), with both LDS sizes
 READOUT_CASES = [
     ("int4_nonsquare", (3, 2), (8, 12), (32, 48), True),     # integer scale, h != w, W < 64: lanes tid >= W inside the one summed wave
     ("frac_small", (2, 3), (6, 10), (20, 36), True),         # non-integer scales, H < 32: one partial row block

@@ -216,7 +216,8 @@ def _attn(mode, kind, q, k, v, out, N, P, D, heads):
 @pytest.mark.parametrize("N,P,D,heads", R.ATTN_SHAPES)
 def test_small_attn_kinds_1_to_4_vs_float64(dev, mode, N, P, D, heads):
     """t2i_attn_kernel (kinds 1 / 3), i2t_attn_lds_kernel / i2t_attn_kernel (kinds 2 / 4) and the scores-passed-in form
-    (l4p_t2i_attn_scores) against small_attn_ref; R.ATTN_SHAPES says which shape reaches which branch.  Kinds 3 / 4 differ from 1 / 2 by a
+    (l4p_t2i_attn_scores) against small_attn_ref; R.ATTN_SHAPES says which shape reaches which branch, and tests/test_track_select_cpu.py
+    asserts the kernel form, grid and LDS size of every (kind, shape, engine) here on the host.  Kinds 3 / 4 differ from 1 / 2 by a
     zero stride only: equal to the per-track call on replicated operands BIT FOR BIT."""
     T = ops.torch_dtype(mode)
     q6, q6r = as_mode(rnd((N, 6, D), 300), mode)
@@ -323,7 +324,8 @@ def _mask_product(mode, up, hyper, N, vox, C):
 def test_mask_product_vs_float64(dev, mode, C):
     """launch_mask_product takes the LDS kernel while 3 C floats + a 128-voxel tile fit 160 KB and the direct kernel otherwise: by that
     size rule the f32 engine with C = 352 (4224 + 128 * 352 * 4 = 184 448 bytes) runs mask_product_kernel and every other (engine, C)
-    here mask_product_lds_kernel (both carry the profiler tag "mask_product", so the branch is taken by construction, not asserted).
+    here mask_product_lds_kernel.  Both carry the profiler tag "mask_product": which kernel each (engine, C, vox, N) here reaches, with
+    its grid and LDS size, is asserted on the host by tests/test_track_select_cpu.py (csrc/track_select.hpp mask_product_select).
     vox = 640: whole tiles; 1000: ragged last tile (104 voxels; LDS-DMA chunks masked by c + tid < chunks); 7: one short tile."""
     for vox in R.MASK_PRODUCT_VOX:
         for N in R.MASK_PRODUCT_N:

@@ -687,8 +687,10 @@ def test_folded_t2i_value_kernels(dev, precision, Cc, knob):
     assert err <= (2e-2 if precision != "32-true" else 1e-5), err
     if precision == "32-true":
         return
-    # the forms for launches that leave CUs idle (a rank's query shard: the context kernel's eight-stage ring, knob track_deep; the head
-    # groups' projection on one wave per 16 x 32 block, knob gemm_skinny) == the chip-filling forms, bit for bit
+    # the forms for launches that leave CUs idle (a rank's query shard; knobs track_deep, gemm_skinny: the head groups' projection on
+    # one wave per 16 x 32 block) == the chip-filling forms, bit for bit.  (P = 608 is no multiple of 64: the CONTEXT kernel is the ring of
+    # four under either setting of track_deep, tests/test_track_select_cpu.py says so; its deep rings are compared by
+    # test_t2i_context_two_stages_per_barrier_equals_the_chip_filling_form below)
     knob("track_deep", 0)
     knob("gemm_skinny", 0)
     cx2 = torch.full((heads * Rg, Cc), float("nan"), dtype=td, device="cuda")

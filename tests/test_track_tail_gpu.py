@@ -1,6 +1,7 @@
-"""The tracker's output tail - l4p_mask_gather and both forms of l4p_track_readout (csrc/track.hip) - against the float64 references of
-tests/kernel_refs.py (checked on the CPU by tests/test_kernel_refs_cpu.py), at the smallest shapes that reach each path of
-launch_track_readout and of the two kernels: R.READOUT_CASES says which case reaches what.
+"""The tracker's output tail - l4p_mask_gather and both forms of l4p_track_readout (csrc/track_readout.hip) - against the float64
+references of tests/kernel_refs.py (checked on the CPU by tests/test_kernel_refs_cpu.py), at the smallest shapes that reach each path of
+launch_track_readout and of the two kernels: R.READOUT_CASES says which case reaches what (held to the selection itself, with grid and
+LDS sizes, by tests/test_track_select_cpu.py).
 
 Every read-out case runs with the knob readout_wide on and off and asserts that the two runs agree bit for bit, that the launch carried
 the tag the case expects (l4p_prof_detail), that the sentinel-filled outputs are fully overwritten with nothing written around them, and
@@ -12,7 +13,7 @@ Peaked logits (one source pixel `span` above the rest): the kernels shift the ex
 bounds the up-sampled maximum from above but is not attained when the peak lies between output samples (the best sample of an interior
 peak at 4x carries weight 0.875^2: its exponent is -0.234 span) or is skipped by a down-sampling grid; with span >= 600 every sample's
 exponential then underflows, z = 0 and traj = 0 / 0.  The kernels therefore repeat the soft-argmax with the exact up-sampled maximum
-when z comes out below 2^-64 (track.hip, READOUT_Z_MIN); the cases here hold both forms to the float64 value on that path as well.
+when z comes out below 2^-64 (track_readout.hip, READOUT_Z_MIN); the cases here hold both forms to the float64 value on that path as well.
 Before that change the seven interior cases with span 600 / 2000 (int4_nonsquare, wide_W, model, lds_over) returned traj = NaN from both
 forms on MI355X and every other case of this file passed.
 No case is skipped: a launch that launch_track_readout refuses is asserted to return L4P_E_INVALID before any launch.
