@@ -2,7 +2,7 @@
 // (reference modeling_finetune.py:169-190: q*scale @ k^T -> softmax -> @ v, 16 heads x 88 dims,
 // 2048 tokens per window).  Never materialises the S x S score matrix.
 //
-// Inputs come straight from the QKV GEMM epilogue (gemm.hpp, EPI_QKV):
+// Inputs come straight from the QKV GEMM epilogue (gemm_epilogue.hpp, EPI_QKV):
 //   q  : [B*S][H*DP]            head dim zero-padded 88 -> DP = 96
 //   kt : K in LDS tile order    8-element groups [b][h][S/KVB][DP/16][KVB][half ^ ((key>>3)&1)]
 //   vt : [B][H][DP][S]          V transposed, so a PV operand fragment is 8 consecutive keys

@@ -8,6 +8,7 @@
 
 #include "attn_select.hpp"
 #include "common.hpp"
+#include "static_for.hpp"
 
 // ---- the constant 16-byte chunks a tile copy substitutes for padding ----
 // row DH of a V^T tile reads ones: O^T[DH][q] = sum_k P[q][k], the softmax denominator with exactly the weights used for O
@@ -43,14 +44,6 @@ struct AttnPad {
     static constexpr int DT_L = DH / 32, HI_L = (I_L >> 2) & 1, R_L = (I_L & 3) + 4 * (I_L >> 3);
     static constexpr int KS_P = DH / 16, HI_P = (DH / 8) & 1;
 };
-
-template <int I, int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    if constexpr (I < N) {
-        f(std::integral_constant<int, I>{});
-        static_for<I + 1, N>(f);
-    }
-}
 
 // XCD-aware work mapping: workgroup L runs on XCD L % 8 (observed dispatch order; speed only, not correctness).  All nqb query blocks
 // of one (batch, head) are given to the SAME XCD so that head's K / V^T (786 KB) is fetched into one L2 instead of eight.

@@ -53,15 +53,7 @@
 //        out (plane 1 of the next slice: issued by tap 20, read at the next tap 0; plane 2: by tap 2, read at tap 9).
 //      - the LDS-DMA queue is never drained: no wait in the loop is vmcnt(0).
 #pragma once
-#include <utility>
-
 #include "gemm.hpp"
-
-// f(integral_constant<int, 0>) ... f(integral_constant<int, N - 1>): a loop whose index is a compile-time constant in its body
-template <int... I, typename F>
-__device__ __forceinline__ void conv_halo_static_for(std::integer_sequence<int, I...>, F&& f) {
-    (f(std::integral_constant<int, I>{}), ...);
-}
 
 template <int WR, int WC>
 struct ConvHaloCfg {
@@ -95,8 +87,6 @@ __device__ __forceinline__ void conv3_halo_body(const GemmParams& p) {
     constexpr int TT = Cfg::TT, TH = Cfg::TH, TW = Cfg::TW, HH = Cfg::HH, HW = Cfg::HW, PR = Cfg::PR, PRP = Cfg::PRP;
     constexpr int WSLOT = Cfg::WSLOT, W_PASS = Cfg::W_PASS, H_PASS = Cfg::H_PASS;
     static_assert(2 * H_PASS <= 9, "planes 2 / 3 are refilled before tap 9");
-    typedef const __attribute__((address_space(1))) void* gptr_t;
-    typedef __attribute__((address_space(3))) void* lptr_t;
 
     extern __shared__ __attribute__((aligned(16))) char smem[];  // [halo NPL x PRP rows x 64 B][W ring 4 x BN x 64 B]
     char* const wring = smem + Cfg::HALO_BYTES;
@@ -111,11 +101,7 @@ __device__ __forceinline__ void conv3_halo_body(const GemmParams& p) {
     //      overlap in its L2 ----
     const int nbw = p.Wo / TW, nbh = p.Ho / TH, nbt = p.To / TT;
     const int ntiles = (p.M / BM);
-    int tile;
-    {
-        const int bid = (int)blockIdx.x, xcd = bid & 7, idx = bid >> 3, q = ntiles >> 3, r = ntiles & 7;
-        tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-    }
+    const int tile = xcd_tile((int)blockIdx.x, ntiles);
     // order of the blocks: T fastest, then w, then h (round 6; round 3 had w, t, h).  The ~32 blocks an XCD runs at a time are then ALL
     // t blocks of a few neighbouring w positions: the two halo planes a block shares with each t neighbour (half of its halo) and
     // the halo columns it shares with its w neighbours are fetched into the XCD's L2 once.  Expected fetch per output plane:
@@ -142,7 +128,7 @@ __device__ __forceinline__ void conv3_halo_body(const GemmParams& p) {
     for (int i = 0; i < W_PASS; ++i) {
         const int s = i * 512 + tid, row = s >> 2, cp = s & 3;
         const int cb = row >> 6, j = (row >> 4) & 3, a = row & 15;
-        const int n = cb * 64 + 16 * (a >> 2) + 4 * j + (a & 3);  // the output column this MFMA row accumulates (gemm.hpp)
+        const int n = cb * 64 + 16 * (a >> 2) + 4 * j + (a & 3);  // the output column this MFMA row accumulates (gemm_epilogue.hpp)
         const int c = cp ^ (((a >> 2) & 1) << 1);
         w_src[i] = (const char*)((const T*)p.W + (long long)n * p.ldw) + c * 16;
     }
@@ -446,7 +432,7 @@ __device__ __forceinline__ void conv3_halo_body(const GemmParams& p) {
         int koff3 = 3 * tap_bytes;     // byte offset of the k range of k-tile t + 3
         for (int cs = 0; cs < ncs; ++cs) {
             const bool more = cs + 1 < ncs;
-            conv_halo_static_for(std::make_integer_sequence<int, 27>{}, [&](auto TAP) {
+            static_for<0, 27>([&](auto TAP) {
                 constexpr int tap = decltype(TAP)::value, dt = tap / 9, dh = tap / 3 % 3, dw = tap % 3;
                 constexpr int aoff = (dt * PRP + dh * HW) * 64;
                 read_w(ws);

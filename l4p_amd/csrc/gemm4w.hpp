@@ -47,7 +47,6 @@ __global__ __launch_bounds__(256, 2) void gemm4w_kernel(const GemmParams p) {
     constexpr int BM = Cfg::BM, BN = Cfg::BN, BK = Cfg::BK, TM = 8, TN = 4;
     constexpr int A_BUF = Cfg::A_BUF;
     constexpr int NPA = 8, NPW = 4, NLD = NPA + NPW;  // LDS-DMA pieces per wave and k-tile (passes of 32 rows)
-    typedef __attribute__((address_space(3))) void* lptr_t;
 
     extern __shared__ __attribute__((aligned(16))) char smem[];  // [A buffer 0 | A buffer 1 | W]
 
@@ -63,6 +62,7 @@ __global__ __launch_bounds__(256, 2) void gemm4w_kernel(const GemmParams p) {
     const int bid = SPLITK ? (int)blockIdx.x - ksplit * ntiles : (int)blockIdx.x;
     int m0, n0;
     {
+        // (xcd_tile + banded_tile of gemm_tile.hpp written out: the calls compile the plain kernel to other instruction text)
         const int xcd = bid & 7, idx = bid >> 3, q = ntiles >> 3, r = ntiles & 7;
         const int tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
         const int nb = (ntn + 7) >> 3, bw = (ntn + nb - 1) / nb, full = (nb - 1) * ntm * bw;
@@ -95,8 +95,7 @@ __global__ __launch_bounds__(256, 2) void gemm4w_kernel(const GemmParams p) {
     for (int i = 0; i < NPA; ++i) {
         int m = m0 + i * 32 + crow;
         if (m >= p.M) m = p.M - 1;  // rows past M are computed on a clamped row and never stored
-        const long long pm = p.a_gr > 0 ? (long long)(m / p.a_gr) * p.a_gs + p.a_go + (m % p.a_gr) : m;
-        a_vo[i] = (unsigned)(pm * p.lda * 2 + cs_a * 16);
+        a_vo[i] = (unsigned)(gemm_a_row(p, m) * p.lda * 2 + cs_a * 16);
     }
 #pragma unroll
     for (int i = 0; i < NPW; ++i) {
@@ -108,8 +107,8 @@ __global__ __launch_bounds__(256, 2) void gemm4w_kernel(const GemmParams p) {
     const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.W, 0, (int)OOB, 0x00020000);
 
     const int nk_all = (p.K + BK - 1) / BK;
-    const int kt0 = SPLITK ? (int)((long long)nk_all * ksplit / nsplit) : 0;
-    const int nk = SPLITK ? (int)((long long)nk_all * (ksplit + 1) / nsplit) - kt0 : nk_all;
+    const int kt0 = SPLITK ? splitk_begin(nk_all, ksplit, nsplit) : 0;
+    const int nk = SPLITK ? splitk_begin(nk_all, ksplit + 1, nsplit) - kt0 : nk_all;
 
     // piece q (0..7: A pass q, 8..11: W pass q - 8) of k-tile kt; A pieces go to A buffer ab.  or_a / or_w[q & 1]: zero, or - in
     // the matrix's last, partial k-tile - bit 31 for the lanes whose chunk lies at or past K: the offset then falls outside the
@@ -151,7 +150,7 @@ __global__ __launch_bounds__(256, 2) void gemm4w_kernel(const GemmParams p) {
     // ---- prologue: k-tile 0 ----
     const bool ktail = (p.K & (BK - 1)) != 0;  // the matrix's last k-tile is partial
     if (ktail && kt0 + 1 == nk_all) tail_or(0);
-    static_for_<0, NLD>([&](auto q_) { stage_piece(q_, 0, std::integral_constant<int, 0>{}); });
+    static_for<0, NLD>([&](auto q_) { stage_piece(q_, 0, std::integral_constant<int, 0>{}); });
 
     // One k-tile on A buffer AB.  LDS reads in issue order: W(kk, j) (8), then A fragment g = kk * 8 + i (16); before MFMA 0 the W
     // reads and PREA A fragments are requested, fragment g + PREA behind the first MFMA of fragment g.  MFMA m: kk = m / 32,
@@ -182,10 +181,10 @@ __global__ __launch_bounds__(256, 2) void gemm4w_kernel(const GemmParams p) {
             else
                 asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(fa[g % RA]) : "v"(a_ad[kk]), "n"(AB * A_BUF + i * 2048) : "memory");
         };
-        static_for_<0, 2 * TN>(rd_w);
-        static_for_<0, PREA>(rd_a);
+        static_for<0, 2 * TN>(rd_w);
+        static_for<0, PREA>(rd_a);
         if (PRIO) __builtin_amdgcn_s_setprio(1);
-        static_for_<0, 2 * TM * TN>([&](auto m_) {
+        static_for<0, 2 * TM * TN>([&](auto m_) {
             constexpr int m = decltype(m_)::value, kk = m / (TM * TN), i = (m % (TM * TN)) / TN, j = m % TN, g = m / TN;
             if constexpr (j == 0) {  // first MFMA of fragment g: reads issued so far = 8 + min(16, PREA + g), fragment g is read 8 + g
                 constexpr int issued = 2 * TN + (PREA + g < 2 * TM ? PREA + g : 2 * TM);

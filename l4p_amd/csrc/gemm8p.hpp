@@ -46,7 +46,7 @@ struct Gemm8pCfg {
 // pointers of the next tile live only across those six stage calls (they are recomputed at the top of the next iteration from an
 // opaque copy of the tile origin): the epilogue's register budget is unchanged.  Matters most where tiles are short: the mask
 // product (K = 352: 5.5 k-tiles per tile, 48 - 96 tiles per CU).
-// SUBPIX (MODE 1 without split-K): the sub-pixel conv (gemm.hpp, subpix_cells): the k-tile sequence of a tile is the active cells of its
+// SUBPIX (MODE 1 without split-K): the sub-pixel conv (gemm_tile.hpp, subpix_cells): the k-tile sequence of a tile is the active cells of its
 // sub-position x Cin / 64 channel slices - the staging counters step through those cells, the phases are untouched - and the epilogue is
 // gemm_epilogue_subpixel.
 // TWOPH (MODE 0 without split-K, not persistent; gemm_select.hpp gemm_8p_two_phase, knob gemm_8p_body): the same k-tile as TWO phases of
@@ -94,8 +94,6 @@ __global__ __launch_bounds__(512) void gemm8p_kernel(const GemmParams p) {
     constexpr int A_HALF = WR * RH * 128, W_HALF = W_PASS * 64 * 128;  // bytes
     constexpr int BUF = 2 * A_HALF + 2 * W_HALF;
     constexpr int INFLIGHT = 2 * A_PASS + 2 * W_PASS;    // loads of the four most recent half-tiles
-    typedef const __attribute__((address_space(1))) void* gptr_t;
-    typedef __attribute__((address_space(3))) void* lptr_t;
 
     extern __shared__ __attribute__((aligned(16))) char smem[];  // [2][A0 | A1 | W0 | W1]
 
@@ -142,31 +140,18 @@ __global__ __launch_bounds__(512) void gemm8p_kernel(const GemmParams p) {
     // (PERSIST: workgroup b's j-th tile is "workgroup" b + j * gridDim.x of the plain launch; gridDim.x is a multiple of 8, so
     //  the XCD of a tile and the block of tiles an XCD works on at a time are those of the plain launch)
     auto decode_tile = [&](int bid, int& m0_, int& n0_) {
-        int tile;
-        {
-            const int xcd = bid & 7, idx = bid >> 3, q = ntiles >> 3, r = ntiles & 7;
-            tile = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + idx;
-        }
+        const int tile = xcd_tile(bid, ntiles);
         int mt, nt_;
-        {
-            const int nb = (ntn + 7) >> 3, bw = (ntn + nb - 1) / nb, full = (nb - 1) * ntm * bw;
 #ifdef GEMM_PROBE_VARIANTS
-            const bool banded = g_tile_gm >= 0;
+        const bool banded = g_tile_gm >= 0;  // (tools/probes: < 0 = plain row-major order)
 #else
-            const bool banded = true;
+        const bool banded = true;
 #endif
-            if (!banded || nb == 1) {
-                mt = tile / ntn;
-                nt_ = tile % ntn;
-            } else if (tile < full) {
-                const int band = tile / (ntm * bw), rem = tile - band * (ntm * bw);
-                mt = rem / bw;
-                nt_ = band * bw + rem % bw;
-            } else {
-                const int w = ntn - (nb - 1) * bw, rem = tile - full;  // last band: the remaining w columns
-                mt = rem / w;
-                nt_ = (nb - 1) * bw + rem % w;
-            }
+        if (banded) {
+            banded_tile(tile, ntn, ntm, mt, nt_);
+        } else {
+            mt = tile / ntn;
+            nt_ = tile % ntn;
         }
         if (MODE == 1) mt = conv_tile_walk(p, mt, BM, 2);
         m0_ = mt * BM, n0_ = nt_ * BN;
@@ -187,10 +172,11 @@ __global__ __launch_bounds__(512) void gemm8p_kernel(const GemmParams p) {
             int m = m0 + (lra / RH) * (TM * 16) + h * RH + lra % RH;
             if (m >= p.M) m = p.M - 1;
             if (MODE == 0) {
-                const long long pm = p.a_gr > 0 ? (long long)(m / p.a_gr) * p.a_gs + p.a_go + (m % p.a_gr) : m;
-                a_src[i][h] = (const char*)((const T*)p.A + pm * p.lda + cs_a * 8);
+                a_src[i][h] = (const char*)((const T*)p.A + gemm_a_row(p, m) * p.lda + cs_a * 8);
                 a_mask[i][h] = 0;
             } else {
+                // (conv_voxel / conv_tap_mask / conv_voxel_index of gemm_tile.hpp written out, and below conv_tap_offset inside this
+                //  kernel's own stream counters: the calls re-allocate the conv kernels' registers - other spills, other text)
                 int wo = m % p.Wo;
                 int r = m / p.Wo;
                 int ho = r % p.Ho;
@@ -228,8 +214,8 @@ __global__ __launch_bounds__(512) void gemm8p_kernel(const GemmParams p) {
     SubpixCells cells{};
     if constexpr (SUBPIX) cells = subpix_cells(p, n0);
     const int nk_all = SUBPIX ? cells.n * kpc : (p.K + BK - 1) / BK;
-    const int kt0 = SPLITK ? (int)((long long)nk_all * ksplit / nsplit) : 0;
-    const int nk = SPLITK ? (int)((long long)nk_all * (ksplit + 1) / nsplit) - kt0 : nk_all;
+    const int kt0 = SPLITK ? splitk_begin(nk_all, ksplit, nsplit) : 0;
+    const int nk = SPLITK ? splitk_begin(nk_all, ksplit + 1, nsplit) - kt0 : nk_all;
     const char* zero = (const char*)g_zero_chunk;
 
     // Conv (MODE 1): k-tile kt is (tap kt / kpc, channel slice kt % kpc).  Both A streams (h = 0, 1) are staged in

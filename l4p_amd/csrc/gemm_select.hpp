@@ -176,14 +176,14 @@ inline bool gemm_is_skinny_grouped(const l4p_gemm_desc& p, const GemmKnobs& k) {
            gemm_tiles(p, 16, 32) <= 512;
 }
 
-// host-side twin of gemm_epilogue_dense_cases (gemm.hpp): the lean dense family
+// host-side twin of gemm_epilogue_dense_cases (gemm_epilogue.hpp): the lean dense family
 inline bool dense_epilogue_is_lean(const l4p_gemm_desc& p) {
     if ((p.tuning & 1) || p.epi != L4P_EPI_DENSE || p.res_mod > 0 || p.c_gr > 0 || p.a_gr > 0) return false;
     const int res = !p.res1 ? 0 : (p.res_f32 ? 1 : 2);
     if (res == 1 && p.res2) return false;
     return (res == 0) || (res == 1 && p.act == L4P_ACT_NONE) || (res == 2 && (p.act == L4P_ACT_NONE || p.act == L4P_ACT_RELU));
 }
-// host-side twin of gemm_epilogue_dense_dispatch (gemm.hpp): true when the kernel will take one of the lean epilogues
+// host-side twin of gemm_epilogue_dense_dispatch (gemm_epilogue.hpp): true when the kernel will take one of the lean epilogues
 inline bool epilogue_is_lean_8p(const l4p_gemm_desc& p) {
     if (p.tuning & 1) return false;
     if (p.epi == L4P_EPI_QKV) return !p.res1 && p.act == L4P_ACT_NONE && p.c_gr == 0;
@@ -219,6 +219,7 @@ inline bool conv_halo_fits(const l4p_gemm_desc& p) {
 // Two-workgroups-per-CU form (gemm4w.hpp): 256 x 128 tiles on 4-wave workgroups, dense GEMM, 16-bit
 inline bool gemm4w_fits(const l4p_gemm_desc& p) {
     if (p.relu_in || p.K % 8 || p.N <= 128) return false;
+    // (one past the largest physical row the device-side map gemm_a_row, gemm_tile.hpp, can return for m < M)
     const long long pm = p.a_gr > 0 ? (long long)((p.M - 1) / p.a_gr) * p.a_gs + p.a_go + p.a_gr : p.M;
     // (LDS-DMA pieces are addressed through 32-bit buffer offsets)
     return pm * p.lda * 2 < (1ll << 31) && (long long)p.N * p.ldw * 2 < (1ll << 31);

@@ -54,8 +54,8 @@ __device__ __forceinline__ void gemm_skinny_loop(const char* xa, const char* wa0
 
     if constexpr (NKS > 0) {
         constexpr int PRE = NKS < RING ? NKS : RING;
-        static_for_<0, PRE>([&](auto d_) { issue(d_, xa, wa0, wa1); });
-        static_for_<0, NKS>([&](auto s_) {
+        static_for<0, PRE>([&](auto d_) { issue(d_, xa, wa0, wa1); });
+        static_for<0, NKS>([&](auto s_) {
             constexpr int s = decltype(s_)::value, d = s % RING;
             constexpr int after = (NKS - 1 - s) < (RING - 1) ? (NKS - 1 - s) : (RING - 1);  // k-steps requested after this one
             landed(std::integral_constant<int, d>{}, std::integral_constant<int, 3 * after>{});
@@ -67,14 +67,14 @@ __device__ __forceinline__ void gemm_skinny_loop(const char* xa, const char* wa0
         });
     } else {
         const int nks = K >> 5;
-        static_for_<0, RING>([&](auto d_) {
+        static_for<0, RING>([&](auto d_) {
             if (decltype(d_)::value < nks) issue(d_, xa, wa0, wa1);
         });
         int s0 = 0;
         // whole turns whose successors are whole too: every step requests its successor a turn ahead, counts are static
         for (; s0 + 2 * RING <= nks; s0 += RING) {
             const char *xn = xa + (long long)(s0 + RING) * 64, *w0n = wa0 + (long long)(s0 + RING) * 64, *w1n = wa1 + (long long)(s0 + RING) * 64;
-            static_for_<0, RING>([&](auto d_) {
+            static_for<0, RING>([&](auto d_) {
                 landed(d_, std::integral_constant<int, 3 * (RING - 1)>{});
                 mfma(d_);
                 issue(d_, xn, w0n, w1n);
@@ -83,8 +83,8 @@ __device__ __forceinline__ void gemm_skinny_loop(const char* xa, const char* wa0
         // the last one or two turns: drained in front of each
         for (; s0 < nks; s0 += RING) {
             const char *xn = xa + (long long)(s0 + RING) * 64, *w0n = wa0 + (long long)(s0 + RING) * 64, *w1n = wa1 + (long long)(s0 + RING) * 64;
-            static_for_<0, RING>([&](auto d_) { landed(d_, std::integral_constant<int, 0>{}); });
-            static_for_<0, RING>([&](auto d_) {
+            static_for<0, RING>([&](auto d_) { landed(d_, std::integral_constant<int, 0>{}); });
+            static_for<0, RING>([&](auto d_) {
                 constexpr int d = decltype(d_)::value;
                 if (s0 + d < nks) {
                     mfma(d_);
@@ -122,7 +122,7 @@ __device__ __forceinline__ void gemm_skinny_body(const GemmParams& p_in, const i
 
     int m = m0 + li;
     if (m >= p.M) m = p.M - 1;  // (rows past M re-read the last row; the epilogue drops them)
-    const long long pm = p.a_gr > 0 ? (long long)(m / p.a_gr) * p.a_gs + p.a_go + (m % p.a_gr) : m;
+    const long long pm = gemm_a_row(p, m);
     const char* xa = (const char*)((const T*)p.A + pm * p.lda + kg * 8);
     // (plain weights are packed with their rows padded to a multiple of 128: rows past N exist and are dropped by the epilogue; a
     //  GROUP's matrix has exactly N rows and the next group's - or nothing - behind them: rows past N re-read row N - 1)

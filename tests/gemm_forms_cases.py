@@ -337,7 +337,7 @@ SWEEP_OUTS = (("T",), ("f32",), ("T", "f32"), ("T", "relu"))
 
 def epilogue_is_lean(case):
     """What the host twins dense_epilogue_is_lean / epilogue_is_lean_8p (csrc/gemm_select.hpp) must return for a dense-epilogue case,
-    stated from the comments of csrc/gemm.hpp ("Lean epilogue for the plain dense family (L4P_EPI_DENSE, no row maps, no broadcast
+    stated from the comments of csrc/gemm_epilogue.hpp ("Lean epilogue for the plain dense family (L4P_EPI_DENSE, no row maps, no broadcast
     residual)", gemm_epilogue_dense_cases): activation x residual kind is one of (any, none), (none, float), (none, T), (ReLU, T), and
     a second residual exists only beside a T one.  The outputs do not enter."""
     if case.res_mod or case.rowmap:

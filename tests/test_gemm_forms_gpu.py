@@ -294,7 +294,7 @@ def test_epilogue_sweep_lean_and_generic(dev, knob, mode, eight_phase):
     non-lean epilogue lean would launch tiles that write nothing (caught by the NaN guard), the other way round by the tag.  On the
     staged 128x64 kernel the tag does not change, the body does.
 
-    Lean against generic (both bodies read: csrc/gemm.hpp gemm_epilogue_dense / gemm_epilogue_row): the same float operations in the same
+    Lean against generic (both bodies read: csrc/gemm_epilogue.hpp gemm_epilogue_dense / gemm_epilogue_row): the same float operations in the same
     order - bias, activation (explicit FMAs, gelu_poly2 = gelu_poly per element), residual, conversion - with ONE exception: two T
     residuals are added as v + (r1 + r2) by the lean body and as (v + r1) + r2 by the generic one.  So outputs are asserted bit-equal,
     and for that combination equal to one output ulp of the element (the form test_layernorm_of_engine_dtype_rows_in_place uses;
