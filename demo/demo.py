@@ -12,6 +12,8 @@ an [RGB | flow | camera-compensated flow] video; with --view4d the 4D video is r
 --static-map DIR (this project's own as well) adds the camray task and fuses the clip's per-frame point clouds into ONE voxel map of
 the static scene (l4p_amd.utils.static_map): a PLY of the voxels seen in at least two frames and outside the motion mask, and its
 counters as .json.
+--objects DIR (this project's own too) adds the camray task and labels the motion mask into moving objects over space-time
+(l4p_amd.utils.moving_objects): per-object boxes, centroids and speeds as .json, the objects' world points as .ply and an overlay video.
 --native DIR (this project's own, --videos / --synthetic) carries the dense results from the network's 224 x 224 grid to the pixel
 grid of the decoded video by guided up-sampling on the GPU (l4p_amd.utils.native_res): depth, flow in source pixels, mask logits,
 validity and the mapped tracks as <seq_name>_native.npz; with --vis also the five-panel video at the source resolution.
@@ -23,6 +25,7 @@ validity and the mapped tracks as <seq_name>_native.npz; with --vis also the fiv
   python demo/demo.py --synthetic --view4d out/        # + the 4D result from a free viewpoint (.mp4 with mediapy, PNG frames without)
   python demo/demo.py --synthetic --scene-flow out/    # + scene flow / camera-compensated flow (.npz, .json, video) under out/
   python demo/demo.py --synthetic --static-map out/    # + one fused voxel map of the static scene (.ply, .json) under out/
+  python demo/demo.py --synthetic --objects out/       # + the moving objects of the clip (.json, .ply, overlay video) under out/
   python demo/demo.py --synthetic --native out/ --vis out/   # + depth / flow / mask at the video's own resolution (.npz, video) under out/
   python demo/demo.py --davis DAVIS_ROOT --ckpt ...    # JPEGImages/480p/<seq>, Annotations/480p/<seq>: queries on the instance masks
   python demo/demo.py --dycheck DYCHECK_ROOT --ckpt ... --recon4d out/   # <seq>/dense/images, <seq>/calibration.txt
@@ -82,6 +85,10 @@ def parse_args(argv=None):
     ap.add_argument("--static-map", default=None, metavar="DIR", dest="static_map",
                     help="also run the camray task and fuse each video's per-frame point clouds into one voxel map of the static scene "
                          "(<seq_name>_static_map.ply, its counters as .json; l4p_amd.utils.static_map.generate_static_map) under DIR")
+    ap.add_argument("--objects", default=None, metavar="DIR",
+                    help="also run the camray task and label the motion mask into moving objects over space-time, frames linked through "
+                         "the backward flow (<seq_name>_objects.json: counters and per-object boxes, centroids and speeds; .ply: the objects' "
+                         "world points; an overlay video; l4p_amd.utils.moving_objects.generate_moving_objects) under DIR")
     ap.add_argument("--native", default=None, metavar="DIR",
                     help="(--videos / --synthetic) write each video's depth, flow (in source pixels), mask logits, validity and tracks at "
                          "the resolution of the decoded frames (<seq_name>_native.npz; guided up-sampling, l4p_amd.utils.native_res) under "
@@ -112,8 +119,9 @@ def parse_args(argv=None):
 def plan(args):
     """(tasks, dataset keyword arguments) of the reference demo's section that ``args`` selects."""
     tasks = ["depth", "flow_2d_backward", "dyn_mask", "track_2d"]  # demo.py:82,99
-    if args.recon4d or args.view4d or args.dycheck or args.scene_flow or args.static_map:
-        tasks.append("camray")  # the reference's 4D sections (demo.py:116-258) add it; scene flow and the static map need the poses too
+    if args.recon4d or args.view4d or args.dycheck or args.scene_flow or args.static_map or args.objects:
+        tasks.append("camray")  # the reference's 4D sections (demo.py:116-258) add it; scene flow, the static map and the objects' 3D tables
+        # need the poses too
     kw = dict(crop_size=(args.frames, 224, 224), estimation_directions=[1, -1] if args.bidirectional else [1],
               track_2d_querry_sampling_spacing=args.spacing)
     if args.davis and (args.recon4d or args.view4d):
@@ -211,6 +219,8 @@ def run(args, model, dataset, tasks):
             scene_flow(batch, out, tasks, args.scene_flow, view4d_dir=args.view4d)
         if args.static_map:
             static_map(batch, out, tasks, args.static_map)
+        if args.objects:
+            objects(batch, out, tasks, args.objects)
         if args.native:
             native(batch, out, tasks, *dataset.source_clip(index), args.native, vis_dir=args.vis)
 
@@ -340,6 +350,27 @@ def static_map(batch, out, tasks, out_dir):
     ratio = c["n_used"] / c["n_kept"] if c["n_kept"] else float("nan")
     print(f"  static map: {c['n_kept']} of {c['n_voxels']} voxels of {float(res['grid'][3]):.3g} kept, {c['n_used']} of {c['n_points']} "
           f"points used ({c['n_masked']} masked), {ratio:.1f} points per voxel; GPU {(t1 - t0) * 1e3:.1f} ms, files "
+          f"{(t2 - t1) * 1e3:.0f} ms -> {name}")
+
+
+def objects(batch, out, tasks, out_dir):
+    """The motion mask labelled into moving objects (l4p_amd.utils.moving_objects): <seq>_objects.json, <seq>_objects.ply and the overlay
+    video <seq>_objects, the GPU part and the file writing timed on their own.  (With --synthetic the seeded weights give an arbitrary
+    mask: the files are written, the objects mean nothing.)"""
+    from l4p_amd.utils import moving_objects as mo
+
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    res = mo.moving_objects_from_outputs(batch, out, tasks)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    name = mo.generate_moving_objects(batch, out, tasks, out_dir, res=res)
+    t2 = time.perf_counter()
+    c = res["counters"]
+    fastest = float(res["speed"].max()) if "speed" in res and res["K"] else float("nan")
+    on = int((res["track_object"] >= 0).sum()) if "track_object" in res else 0
+    print(f"  objects: {c['n_kept']} of {c['n_components']} components kept, {c['n_kept_pixels']} of {c['n_foreground']} foreground pixels "
+          f"({c['n_pixels']} in all), fastest step {fastest:.3g}, {on} tracks on objects; GPU {(t1 - t0) * 1e3:.1f} ms, files "
           f"{(t2 - t1) * 1e3:.0f} ms -> {name}")
 
 

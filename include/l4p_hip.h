@@ -43,7 +43,9 @@ typedef void* l4p_stream; /* hipStream_t */
 typedef struct l4p_engine l4p_engine;
 
 const char* l4p_last_error(void);
-int l4p_abi_version(void); /* 24: results at the video's own resolution (l4p_guided_upsample);
+int l4p_abi_version(void); /* 25: moving objects (l4p_objects_ws_bytes, l4p_objects_label, l4p_objects_roots, l4p_objects_tables_ws_bytes,
+                              * l4p_objects_tables, l4p_objects_tracks, l4p_objects_overlay);
+                              * 24: results at the video's own resolution (l4p_guided_upsample);
                               * 23: the static scene map (l4p_static_map_ws_bytes, l4p_static_map_insert, l4p_static_map_count, l4p_static_map_emit);
                               * 22: dense scene flow and camera-compensated flow (l4p_scene_flow, l4p_scene_flow_summary, l4p_scene_flow_colors);
                               * 21: tracking in both time directions (l4p_time_reverse, l4p_track_bidir_queries, l4p_track_bidir_merge);
@@ -619,6 +621,73 @@ int l4p_static_map_count(l4p_stream stream, void* ws, int T, int HW, long long c
 int l4p_static_map_emit(l4p_stream stream, void* ws, const float* grid, int T, int HW, long long capacity, long long n_kept, float* xyz,
                         unsigned char* rgb, int* count, int* n_frames, int* first_frame, int* last_frame, int* first_point,
                         long long* key, int* voxel_id);
+
+/* ------------------------------------------------------------------------------------------------
+ * Moving objects (csrc/objects.hip; this project's own, the reference thresholds the motion mask for a picture and stops; DESIGN.md
+ * "Moving objects"): connected-component labelling of the motion mask over (t, y, x), the frames linked through the backward flow, and
+ * the per-object tables that follow from the labels.  One clip (batch size 1).  All arithmetic is f32 and every operation is rounded
+ * on its own.  Inputs, with linear index m = (t H + y) W + x, T H W <= 2^30:
+ *   mask_logit [T][H][W] float;  depth [T][H][W] float or NULL;  flow [2][T][H][W] float or NULL: backward flow, channel 0 = x (pixel p
+ *   of frame t is found at p + flow in frame t - 1, as l4p_scene_flow reads it);  keep [T][H][W] uchar or NULL.
+ * Foreground: m is foreground iff mask_logit[m] > 0 (a NaN is not > 0), and keep is NULL or keep[m] != 0, and depth is NULL or
+ *   depth[m] is finite and > 0.
+ * Spatial edges: a foreground pixel (t, y, x) has an edge to (t, y, x-1) and (t, y-1, x); with connectivity == 8 also to (t, y-1, x-1)
+ *   and (t, y-1, x+1).  An edge exists where the neighbour is inside the frame and foreground and the depth gate passes.  The gate
+ *   passes when depth is NULL, or max_depth_ratio <= 0, or fmaxf(da, db) <= max_depth_ratio * fminf(da, db).
+ * Temporal edge, for t >= 1: one edge to (t-1, yq, xq) if that pixel is foreground.  Without flow (yq, xq) = (y, x).  With flow:
+ *   u = flow[0][m], v = flow[1][m]; no edge if either is not finite; gx = floorf(((float)x + u) + 0.5f), gy = floorf(((float)y + v) +
+ *   0.5f); no edge unless gx >= 0 && gx < (float)W && gy >= 0 && gy < (float)H, compared in float, before the conversion to int;
+ *   (xq, yq) = ((int)gx, (int)gy).  Temporal edges carry no depth gate: camera and object both move between frames.
+ * Component: a connected set under these edges; its label is the smallest m among its members, so no output depends on the order in
+ *   which edges are processed.  label [M] int = that value, -1 for background.  Per component: n_pixels, first_frame = label / (H W),
+ *   last_frame.  Edges change t by at most one, so a component's frames are contiguous: n_frames = last_frame - first_frame + 1.
+ * Filter and order: a component is kept iff n_pixels >= min_pixels and n_frames >= min_frames; kept components are numbered 0..K-1 by
+ *   ascending label, the order of first appearance.  object_id [M] int = that number, or -1.
+ * counters [6] unsigned long long on the device = n_pixels (T H W), n_foreground, n_components, n_kept, n_kept_pixels, n_guard.
+ *   Every find and union loop of the labelling is finite (parent[i] <= i from the first write on, only smaller values are written);
+ *   each still carries a cap on its steps (T H W on the global array), and a loop that hits it gives up and counts in n_guard
+ *   instead of spinning: n_guard != 0 means the labels are not to be used.
+ * Calls: l4p_objects_label (ws of l4p_objects_ws_bytes(T, H, W) bytes, 0 for sizes the entries refuse; every byte of ws that is read
+ *   is written by the call first) writes label, object_id and counters; the caller reads counters back to size the tables;
+ *   l4p_objects_roots (same ws, label and object_id, n_kept as counted) writes root, n_pixels, first_frame, last_frame [K] int.
+ *
+ * Per-object tables, l4p_objects_tables (ws of l4p_objects_tables_ws_bytes(K, T) bytes, K T <= 2^27), one launch over the pixels and
+ * one over (k, t).  From integers only: count [K][T] int; bbox [K][T][4] int = x0, y0, x1, y1 inclusive, (0, 0, -1, -1) where count is
+ *   0; centroid_px [K][T][2] float = (float)((double)sum / (double)count) of the integer sums of x and of y, 0 where count is 0.
+ * With points [T H W][3] float (NULL: no 3D tables, the five 3D outputs are not written) and grid [4] float = (ox, oy, oz, v): a pixel's
+ *   point is valid iff v > 0 and v is finite, every coordinate is finite, and per axis, with q = (p - o) / v, s = floorf(q * 256.0f)
+ *   lies in [-2^28, 2^28).  The three sums of (long long)s are 64-bit integer atomics.  count3d [K][T] int = n, the valid points;
+ *   centroid_xyz [K][T][3] float = (float)((double)o + (((double)sum + 0.5 * (double)n) / ((double)n * 256.0)) * (double)v), in f64,
+ *   every operation rounded on its own, 0 where n = 0;  box3d [K][T][6] float = per-axis minimum (3) and maximum (3) of the valid
+ *   points (-0 orders below +0), 0 where n = 0;  step [K][T][3] = the f32 difference of the rounded centroids of frames t and t - 1, 0
+ *   where either has n = 0 and on frame 0;  speed [K][T] = sqrtf((dx * dx + dy * dy) + dz * dz).
+ *   No float sum is accumulated by atomics anywhere.
+ *
+ * Tracks on objects, l4p_objects_tracks, one thread per track: traj [N][2][T] float (x, y), vis [N][T] float (visibility logits).
+ *   Track n is sampled at frame t iff vis > 0, x and y are finite, and gx = floorf(x + 0.5f), gy = floorf(y + 0.5f) lie inside the
+ *   frame by the float comparison above.  track_object_nt [N][T] int = object_id under that pixel, or -1;  track_object [N] int = the
+ *   non-negative id with the most sampled frames, ties to the smallest id, -1 when there is none;  votes [N] int = that count.
+ *
+ * Overlay, l4p_objects_overlay: frames, out [T][H][W][3] uchar, lut [K][3] uchar, alpha in [0, 256].  A pixel with id k in [0, K) becomes
+ *   (rgb * (256 - alpha) + lut[k] * alpha + 128) >> 8 per channel; other pixels are copied.
+ *
+ * Every entry returns L4P_E_INVALID, with nothing launched, for a size it refuses or a null pointer it needs; K = 0 and N = 0 are
+ * accepted and launch nothing.
+ * ---------------------------------------------------------------------------------------------- */
+size_t l4p_objects_ws_bytes(int T, int H, int W);
+int l4p_objects_label(l4p_stream stream, const float* mask_logit, const float* depth, const float* flow, const unsigned char* keep, int T,
+                      int H, int W, int connectivity, float max_depth_ratio, int min_pixels, int min_frames, void* ws, int* label,
+                      int* object_id, unsigned long long* counters);
+int l4p_objects_roots(l4p_stream stream, const void* ws, const int* label, const int* object_id, int T, int H, int W, long long n_kept,
+                      int* root, int* n_pixels, int* first_frame, int* last_frame);
+size_t l4p_objects_tables_ws_bytes(int K, int T);
+int l4p_objects_tables(l4p_stream stream, const int* object_id, const float* points, const float* grid, int T, int H, int W, int K,
+                       void* ws, int* count, int* bbox, float* centroid_px, int* count3d, float* centroid_xyz, float* box3d, float* step,
+                       float* speed);
+int l4p_objects_tracks(l4p_stream stream, const int* object_id, const float* traj, const float* vis, int N, int T, int H, int W,
+                       int* track_object_nt, int* track_object, int* votes);
+int l4p_objects_overlay(l4p_stream stream, const unsigned char* frames, const int* object_id, const unsigned char* lut, int T, int H,
+                        int W, int K, int alpha, unsigned char* out);
 
 /* ------------------------------------------------------------------------------------------------
  * Native-resolution results (csrc/upsample.hip; this project's own, the reference stops at 224 x 224; DESIGN.md "Native-resolution
