@@ -14,6 +14,9 @@ the static scene (l4p_amd.utils.static_map): a PLY of the voxels seen in at leas
 counters as .json.
 --objects DIR (this project's own too) adds the camray task and labels the motion mask into moving objects over space-time
 (l4p_amd.utils.moving_objects): per-object boxes, centroids and speeds as .json, the objects' world points as .ply and an overlay video.
+--object-models DIR (this project's own too) adds the camray task and fits every moving object's rigid motion per frame, then fuses
+the object's points of all frames into ONE model in the pose of its first frame (l4p_amd.utils.object_motion): the models as .ply,
+the motions, poses and fit counters as .json.
 --native DIR (this project's own, --videos / --synthetic) carries the dense results from the network's 224 x 224 grid to the pixel
 grid of the decoded video by guided up-sampling on the GPU (l4p_amd.utils.native_res): depth, flow in source pixels, mask logits,
 validity and the mapped tracks as <seq_name>_native.npz; with --vis also the five-panel video at the source resolution.
@@ -26,6 +29,7 @@ validity and the mapped tracks as <seq_name>_native.npz; with --vis also the fiv
   python demo/demo.py --synthetic --scene-flow out/    # + scene flow / camera-compensated flow (.npz, .json, video) under out/
   python demo/demo.py --synthetic --static-map out/    # + one fused voxel map of the static scene (.ply, .json) under out/
   python demo/demo.py --synthetic --objects out/       # + the moving objects of the clip (.json, .ply, overlay video) under out/
+  python demo/demo.py --synthetic --object-models out/ # + one fused model per moving object and its motion (.ply, .json) under out/
   python demo/demo.py --synthetic --native out/ --vis out/   # + depth / flow / mask at the video's own resolution (.npz, video) under out/
   python demo/demo.py --davis DAVIS_ROOT --ckpt ...    # JPEGImages/480p/<seq>, Annotations/480p/<seq>: queries on the instance masks
   python demo/demo.py --dycheck DYCHECK_ROOT --ckpt ... --recon4d out/   # <seq>/dense/images, <seq>/calibration.txt
@@ -89,6 +93,10 @@ def parse_args(argv=None):
                     help="also run the camray task and label the motion mask into moving objects over space-time, frames linked through "
                          "the backward flow (<seq_name>_objects.json: counters and per-object boxes, centroids and speeds; .ply: the objects' "
                          "world points; an overlay video; l4p_amd.utils.moving_objects.generate_moving_objects) under DIR")
+    ap.add_argument("--object-models", default=None, metavar="DIR", dest="object_models",
+                    help="also run the camray task, fit every moving object's rigid motion per frame from its flow-linked pixel pairs and "
+                         "fuse its points of all frames into one model (<seq_name>_object_models.ply, <seq_name>_object_motion.json; "
+                         "l4p_amd.utils.object_motion.generate_object_models) under DIR")
     ap.add_argument("--native", default=None, metavar="DIR",
                     help="(--videos / --synthetic) write each video's depth, flow (in source pixels), mask logits, validity and tracks at "
                          "the resolution of the decoded frames (<seq_name>_native.npz; guided up-sampling, l4p_amd.utils.native_res) under "
@@ -119,7 +127,7 @@ def parse_args(argv=None):
 def plan(args):
     """(tasks, dataset keyword arguments) of the reference demo's section that ``args`` selects."""
     tasks = ["depth", "flow_2d_backward", "dyn_mask", "track_2d"]  # demo.py:82,99
-    if args.recon4d or args.view4d or args.dycheck or args.scene_flow or args.static_map or args.objects:
+    if args.recon4d or args.view4d or args.dycheck or args.scene_flow or args.static_map or args.objects or args.object_models:
         tasks.append("camray")  # the reference's 4D sections (demo.py:116-258) add it; scene flow, the static map and the objects' 3D tables
         # need the poses too
     kw = dict(crop_size=(args.frames, 224, 224), estimation_directions=[1, -1] if args.bidirectional else [1],
@@ -221,6 +229,8 @@ def run(args, model, dataset, tasks):
             static_map(batch, out, tasks, args.static_map)
         if args.objects:
             objects(batch, out, tasks, args.objects)
+        if args.object_models:
+            object_models(batch, out, tasks, args.object_models)
         if args.native:
             native(batch, out, tasks, *dataset.source_clip(index), args.native, vis_dir=args.vis)
 
@@ -371,6 +381,26 @@ def objects(batch, out, tasks, out_dir):
     on = int((res["track_object"] >= 0).sum()) if "track_object" in res else 0
     print(f"  objects: {c['n_kept']} of {c['n_components']} components kept, {c['n_kept_pixels']} of {c['n_foreground']} foreground pixels "
           f"({c['n_pixels']} in all), fastest step {fastest:.3g}, {on} tracks on objects; GPU {(t1 - t0) * 1e3:.1f} ms, files "
+          f"{(t2 - t1) * 1e3:.0f} ms -> {name}")
+
+
+def object_models(batch, out, tasks, out_dir):
+    """Every moving object's rigid motion per frame and its fused model (l4p_amd.utils.object_motion): <seq>_object_models.ply and
+    <seq>_object_motion.json, the GPU part and the file writing timed on their own.  (With --synthetic the seeded weights give an
+    arbitrary mask: the files are written, the models mean nothing.)"""
+    from l4p_amd.utils import object_motion as om
+
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    res = om.object_motion_from_outputs(batch, out, tasks)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    name = om.generate_object_models(batch, out, tasks, out_dir, res=res)
+    t2 = time.perf_counter()
+    mo, md = res["motion"], res["models"]
+    rows = int(mo["valid"].sum()) if res["K"] else 0
+    print(f"  object models: {res['K']} objects, {rows} valid motions of {int((mo['n_pairs'] > 0).sum()) if res['K'] else 0} rows with pairs, "
+          f"{md['offsets'][-1]} model vertices from {res['counters']['n_kept_pixels']} object pixels; GPU {(t1 - t0) * 1e3:.1f} ms, files "
           f"{(t2 - t1) * 1e3:.0f} ms -> {name}")
 
 

@@ -43,7 +43,9 @@ typedef void* l4p_stream; /* hipStream_t */
 typedef struct l4p_engine l4p_engine;
 
 const char* l4p_last_error(void);
-int l4p_abi_version(void); /* 25: moving objects (l4p_objects_ws_bytes, l4p_objects_label, l4p_objects_roots, l4p_objects_tables_ws_bytes,
+int l4p_abi_version(void); /* 26: object motion and models (l4p_objects_motion_ws_bytes, l4p_objects_motion, l4p_objects_canonical,
+                              * l4p_objects_place);
+                              * 25: moving objects (l4p_objects_ws_bytes, l4p_objects_label, l4p_objects_roots, l4p_objects_tables_ws_bytes,
                               * l4p_objects_tables, l4p_objects_tracks, l4p_objects_overlay);
                               * 24: results at the video's own resolution (l4p_guided_upsample);
                               * 23: the static scene map (l4p_static_map_ws_bytes, l4p_static_map_insert, l4p_static_map_count, l4p_static_map_emit);
@@ -688,6 +690,66 @@ int l4p_objects_tracks(l4p_stream stream, const int* object_id, const float* tra
                        int* track_object_nt, int* track_object, int* votes);
 int l4p_objects_overlay(l4p_stream stream, const unsigned char* frames, const int* object_id, const unsigned char* lut, int T, int H,
                         int W, int K, int alpha, unsigned char* out);
+
+/* ------------------------------------------------------------------------------------------------
+ * Object motion and models (csrc/object_motion.hip; this project's own; DESIGN.md "Object motion and models"): per object and frame
+ * the rigid motion from frame t - 1 to frame t in the world frame, the poses composed from it, and the object's points carried into
+ * the pose of its first frame.  One clip (batch size 1).  Inputs, with m = (t H + y) W + x, H W <= 2^20, T H W <= 2^30, K T <= 2^27:
+ *   object_id [T][H][W] int and K as l4p_objects_label writes them (ids outside [0, K) are background);  points [T H W][3] float, the
+ *   world points, frame-major;  flow [2][T][H][W] float or NULL, backward flow, channel 0 = x;  grid [4] float = (ox, oy, oz, v).
+ * Pairs.  For t >= 1, pixel m of frame t with object_id[m] = k in [0, K) has the predecessor m' = ((t-1) H + yq) W + xq, found exactly
+ *   as the temporal edge of l4p_objects_label: without flow (xq, yq) = (x, y); with flow u = flow[0][m], v = flow[1][m], no pair if
+ *   either is not finite, gx = floorf(((float)x + u) + 0.5f), gy = floorf(((float)y + v) + 0.5f), no pair unless gx >= 0 && gx <
+ *   (float)W && gy >= 0 && gy < (float)H compared in float, (xq, yq) = ((int)gx, (int)gy).  The pair exists iff object_id[m'] == k and
+ *   both points are valid by the rule of l4p_objects_tables: v > 0 and finite, every coordinate finite and per axis
+ *   s = floorf(((p - o) / v) * 256.0f) in [-2^28, 2^28), f32, every operation rounded on its own.  a = the triple (long long)s of
+ *   points[m'] (frame t - 1), b = that of points[m] (frame t).  The motion of row (k, t) is b ~ R a + t, no scale.
+ * Moments: 64-bit integer sums by integer atomics (a wave first adds up runs of lanes on one (k, t) by shuffles); no float is summed
+ *   by atomics.  2 + n_refits passes over the pixels.
+ *   1. Centres: per (k, t) n_pairs = n, sum a [3], sum b [3] (and the row's pixels, pairs or not: an object's first frame is the first
+ *      t with a pixel).  c_a = floor(sum a / n), c_b = floor(sum b / n), integer floor division per axis; 0 with n = 0.
+ *   2. Fit: d_a = a - c_a, d_b = b - c_b.  A pair with any |d| >= 2^21 is dropped and counted in n_far (every product is then below
+ *      2^42 and a sum of products over at most H W <= 2^20 pairs below 2^62; the two sums of squares, three products a pair, stay
+ *      below 3 * 2^62 < 2^64: they are accumulated and read as unsigned 64-bit, and moments holds their bit pattern).  moments [18] = n, sum d_a [3], sum d_b [3], sum d_b d_a^T [9]
+ *      (row-major: entry 3 i + j = sum d_b[i] d_a[j]), sum |d_a|^2, sum |d_b|^2.
+ *   3. Refit, n_refits times: the same moments about the same centres over the pairs that are not far and pass, with the previous
+ *      round's emitted f32 motion (R, t) and the raw f32 points pa = points[m'], pb = points[m], all f32, each operation rounded:
+ *        pred_i = ((R[i][0] pa.x + R[i][1] pa.y) + R[i][2] pa.z) + t[i];   d = pred - pb;   tau = inlier_voxels * v;
+ *        (d.x d.x + d.y d.y) + d.z d.z <= tau tau        (a NaN fails).
+ *   n_inliers = n of the last round; n_far is the same in every round.
+ * Solve, per (k, t) after each fit pass, f64, every operation rounded on its own, S = (double) of a moment, q = (double)v / 256.0:
+ *   C[i][j] = S_ba[i][j] - (S_b[i] S_a[j]) / n;   Saa = S_aa - ((S_a.x S_a.x + S_a.y S_a.y) + S_a.z S_a.z) / n;   Sbb likewise;
+ *   valid = n_inliers >= min_pairs (min_pairs >= 3);   R = the rotation of the closed form of csrc/umeyama_moments.hpp
+ *   (umeyama_rotation) on cov = C / n when valid, else I;
+ *   A[i] = (double)o[i] + (((double)c_a[i] + S_a[i] / n) + 0.5) q,  B likewise (the half is the bias of the floor, as in the tables'
+ *   centroid);   t[i] = B[i] - ((R[i][0] A.x + R[i][1] A.y) + R[i][2] A.z);
+ *   rms = q sqrt(fmax(0, ((Sbb + Saa) - 2 tr) / n)),  tr = sum over i, j in row-major order of R[i][j] C[i][j].
+ *   A row with n_inliers = 0 (no pairs, frame 0, every frame up to the object's first) gets R = I, t = 0, rms = 0; a row with
+ *   1 <= n_inliers < min_pairs gets R = I and hence t = B - A, the step of the pairs' centroid.
+ * Outputs: motion [K][T][12] float = R row-major, then t, each rounded once from f64;  n_pairs, n_inliers, n_far [K][T] int;
+ *   rms [K][T] float;  valid [K][T] uchar;  moments [K][T][18] long long or NULL: the last round's sums.
+ * Composition, one thread per object, f64 over the emitted f32 motions M: first = the first frame with a pixel of k (T if none);
+ *   G[t] = I for t <= first, G[t] = M[k][t] G[t - 1] after it (R = (M.R G.R row by column, ((a b + c d) + e f)), t = ((M.R G.t)) +
+ *   M.t).  pose [K][T][12] float = G rounded;  pose_valid [K][T] uchar = 1 iff valid[k][u] for every first < u <= t.
+ * Canonical points, l4p_objects_canonical (needs the ws that l4p_objects_motion left, same K and T): for a pixel of object k,
+ *   canonical[m] = (float)(((Ri[i][0] (double)p.x + Ri[i][1] (double)p.y) + Ri[i][2] (double)p.z) + ti[i]) with the inverse of
+ *   G[k][t] formed in f64: Ri = G.R^T, ti[i] = -((G.R[0][i] G.t.x + G.R[1][i] G.t.y) + G.R[2][i] G.t.z); every other pixel gets NaN
+ *   (l4p_static_map_insert drops it as non-finite).
+ * Placement, l4p_objects_place: rows xyz [V][3] float with object [V] int carried to frame t by the f32 pose, in f32:
+ *   out[i] = ((R[i][0] x + R[i][1] y) + R[i][2] z) + t[i] of pose[object][t]; NaN for an object outside [0, K).
+ * ws: l4p_objects_motion_ws_bytes(K, T) bytes (0 for sizes the entries refuse); every byte that is read is written by
+ *   l4p_objects_motion first.  Every entry returns L4P_E_INVALID, with nothing launched, for a size or value it refuses or a null
+ *   pointer it needs; K = 0 launches nothing in l4p_objects_motion (l4p_objects_canonical then writes NaN everywhere), V = 0 nothing.
+ * ---------------------------------------------------------------------------------------------- */
+size_t l4p_objects_motion_ws_bytes(int K, int T);
+int l4p_objects_motion(l4p_stream stream, const int* object_id, const float* points, const float* flow, const float* grid, int T, int H,
+                       int W, int K, int n_refits, float inlier_voxels, int min_pairs, void* ws, float* motion, int* n_pairs,
+                       int* n_inliers, int* n_far, float* rms, unsigned char* valid, long long* moments, float* pose,
+                       unsigned char* pose_valid);
+int l4p_objects_canonical(l4p_stream stream, const int* object_id, const float* points, const void* ws, int T, int H, int W, int K,
+                          float* canonical);
+int l4p_objects_place(l4p_stream stream, const float* xyz, const int* object, const float* pose, long long V, int K, int T, int t,
+                      float* out);
 
 /* ------------------------------------------------------------------------------------------------
  * Native-resolution results (csrc/upsample.hip; this project's own, the reference stops at 224 x 224; DESIGN.md "Native-resolution

@@ -18,7 +18,7 @@ from typing import Optional
 
 from . import _header
 
-ABI_VERSION = 25  # what l4p_abi_version() of the library this binding was written against returns (include/l4p_hip.h)
+ABI_VERSION = 26  # what l4p_abi_version() of the library this binding was written against returns (include/l4p_hip.h)
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "l4p_hip.h")

@@ -25,7 +25,7 @@ void l4p_set_error(const char* fmt, ...) {
 extern "C" {
 
 const char* l4p_last_error(void) { return g_err; }
-int l4p_abi_version(void) { return 25; }
+int l4p_abi_version(void) { return 26; }
 
 // A HIP stream whose kernels run on CUs [first_cu, first_cu + n_cus) only (hipExtStreamCreateWithCUMask): the sharded long-video path
 // gives the tracker's latency-bound kernel chain a slice of the chip of its own, beside the chip-filling decoders on the rest.

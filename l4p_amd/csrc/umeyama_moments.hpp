@@ -45,10 +45,11 @@ static UMEYAMA_FN void jacobi3(double A[3][3], double V[3][3]) {
     }
 }
 
-// model: [0..8] = s*R row-major, [9..11] = t, [12] = s
-template <typename OutT>
-UMEYAMA_FN void umeyama_from_moments(const double ms[3], const double md[3], const double cov[3][3], double var_s,
-                                     OutT* model) {
+// The rotation of the closed form on its own: R (a proper rotation at every rank of cov, I for cov = 0) and the sum of the singular
+// values with the reflection sign folded into the third, sigma1 + sigma2 +- sigma3 = tr(R^T cov).  Nothing here is divided by a
+// variance or multiplied by a scale, so a caller that wants a rigid motion (csrc/object_motion.hip) takes R as it stands;
+// tests/umeyama_rotation_main.cpp runs this entry on the CPU against the float64 SVD.
+static UMEYAMA_FN void umeyama_rotation(const double cov[3][3], double R[3][3], double* sigma_sum) {
     double AtA[3][3], V[3][3];
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) AtA[i][j] = cov[0][i] * cov[0][j] + cov[1][i] * cov[1][j] + cov[2][i] * cov[2][j];
@@ -110,10 +111,18 @@ UMEYAMA_FN void umeyama_from_moments(const double ms[3], const double md[3], con
     // sigma3 with the reflection sign folded in: u3^T cov v3 (negative when det(cov) < 0)
     double s3 = 0;
     for (int i = 0; i < 3; ++i) s3 += u3[i] * (cov[i][0] * v3[0] + cov[i][1] * v3[1] + cov[i][2] * v3[2]);
-    const double scale = var_s > 0 ? (s1 + s2 + s3) / var_s : 1.0;
-    double R[3][3];
+    *sigma_sum = s1 + s2 + s3;
     for (int i = 0; i < 3; ++i)
         for (int j = 0; j < 3; ++j) R[i][j] = u1[i] * v1[j] + u2[i] * v2[j] + u3[i] * v3[j];
+}
+
+// model: [0..8] = s*R row-major, [9..11] = t, [12] = s
+template <typename OutT>
+UMEYAMA_FN void umeyama_from_moments(const double ms[3], const double md[3], const double cov[3][3], double var_s,
+                                     OutT* model) {
+    double R[3][3], sigma_sum;
+    umeyama_rotation(cov, R, &sigma_sum);
+    const double scale = var_s > 0 ? sigma_sum / var_s : 1.0;
     for (int i = 0; i < 3; ++i) {
         for (int j = 0; j < 3; ++j) model[i * 3 + j] = (OutT)(scale * R[i][j]);
         model[9 + i] = (OutT)(md[i] - scale * (R[i][0] * ms[0] + R[i][1] * ms[1] + R[i][2] * ms[2]));
